@@ -7,8 +7,14 @@ normalisation), the Gram recursion kernel with the fused normalisation / sigma*v
 epilogue, and -- at N > 1 GPUs -- the RCCL all-gather of the row blocks plus the gfx950 mirror
 assembly, so every rank ends with the full N x N matrix ("scaling": "strong": the total Gram is fixed).
 
-    python bench.py                        # N=1, headline workload
+    python bench.py                        # N=1, headline workload: set up, warm up, time, one line
+    python bench.py --full                 # + HBM copy probe, float64 parity subsample, CPU baseline
+    python bench.py --dump-outputs DIR     # + DIR/K.npy, the Gram of the last timed step
     torchrun --nproc-per-node 8 bench.py --gpus 8
+
+A plain run does what the headline needs and no more; the roofline and breakdown fields it still carries
+come from the HIP events the timed steps record anyway.  What takes work of its own -- the HBM copy probe,
+the float64 oracle parity subsample (max_abs_err) and the CPU baseline -- runs with --full only.
 
 Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md "Measurement").
 """
@@ -151,6 +157,27 @@ def hbm_copy_probe(dev, nbytes=1 << 30, reps=20):
     return gbs
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs keeps every file set well under 64 MB
+
+
+def dump_outputs(dirname, K):
+    """Write the array a caller of the timed path receives -- the normalised Gram K of the last timed
+    step -- as DIR/K.npy (float32).  A Gram above DUMP_MAX_BYTES is cut to a fixed, seeded (seed 0) sorted
+    sample of its rows, every column kept; the sample depends on the shape alone, so two builds run with
+    the same arguments write the same entries.  Returns what was written, for the result line."""
+    os.makedirs(dirname, exist_ok=True)
+    n_rows, n_cols = K.shape
+    keep = min(n_rows, max(1, DUMP_MAX_BYTES // (4 * n_cols)))
+    if keep < n_rows:
+        import torch
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+        K = K[torch.as_tensor(rows, device=K.device)]
+    arr = np.ascontiguousarray(K.float().cpu().numpy())
+    np.save(os.path.join(dirname, "K.npy"), arr)
+    return {"K": {"file": "K.npy", "dtype": "float32", "shape": list(arr.shape),
+                  "rows": "all" if keep == n_rows else f"seed-0 sorted sample of {keep} of {n_rows} rows"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -158,10 +185,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="H", choices=sorted(WORKLOADS))
     ap.add_argument("--nseq", "--n", dest="n", type=int, help="override the workload N")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the HBM copy probe, the float64 parity subsample and the "
+                         "CPU baseline (a plain run only times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the Gram of the last timed step to DIR/K.npy (float32; see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the HBM copy-bandwidth probe")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the float64 parity subsample")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: skip the HBM copy-bandwidth probe")
     ap.add_argument("--seed-engine", default="valu", choices=["valu", "mfma"],
                     help="RBF seed dots on packed VALU FMAs (default) or on the matrix cores (A/B arm)")
     ap.add_argument("--gram-path", default="fused", choices=["fused", "split"],
@@ -284,7 +316,8 @@ def main():
             prof = json.load(f)
         traffic = prof.get("hbm_bytes_per_launch")
 
-    probe = hbm_copy_probe(dev) if rank == 0 and not args.no_probe else None
+    dumped = dump_outputs(args.dump_outputs, K) if rank == 0 and args.dump_outputs else None
+    probe = hbm_copy_probe(dev) if rank == 0 and args.full and not args.no_probe else None
     value = args.steps * n * n / elapsed
     out = {
         "metric": "sig-kernel Gram entries/sec (N, len L, dim D, level M); max-abs err vs ref",
@@ -337,7 +370,9 @@ def main():
                               "gathered_bytes": world * 2 * gdist.triangle_chunks(n, world)[1] * n * 4}
     else:
         out["breakdown"] = mine
-    if rank == 0 and not args.no_check:
+    if dumped:
+        out["dumped"] = dumped
+    if rank == 0 and args.full and not args.no_check:
         # parity on a bounded subsample (256 rows): the normalised Gram restricted to a subset
         # S of the sequences equals K(X[S]) (per-sequence diagonals), evaluated by the float64 oracle
         S = np.unique(np.linspace(0, n - 1, min(n, args.check_rows)).astype(int))
@@ -347,7 +382,7 @@ def main():
         out["max_abs_err"] = float(np.abs(got - Kref).max())
         out["max_abs_ref"] = float(np.abs(Kref).max())
         out["check_rows"] = len(S)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(l, d, m, seconds=args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

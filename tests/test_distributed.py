@@ -215,8 +215,8 @@ def test_bench_world2_gloo_breakdown(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--nseq", "256", "--backend", "gloo", "--no-cpu",
-           "--no-probe", "--check-rows", "32"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--nseq", "256", "--backend", "gloo", "--full",
+           "--no-cpu", "--no-probe", "--check-rows", "32"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]

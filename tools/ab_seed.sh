@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for wl in H C5; do
   for eng in valu mfma; do
     steps=5; [ $wl = C5 ] && steps=2
-    timeout -k 10 240 python3 -u bench.py --workload $wl --seed-engine $eng --steps $steps --warmup 1 --no-cpu --no-probe \
+    timeout -k 10 240 python3 -u bench.py --workload $wl --seed-engine $eng --steps $steps --warmup 1 --full --no-cpu --no-probe \
       > "$OUT/bench_${wl}_${eng}.json" 2> "$OUT/bench_${wl}_${eng}.err" || exit 1
     cat "$OUT/bench_${wl}_${eng}.json"
   done

@@ -13,6 +13,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-me
 r=$?; tail -5 "$OUT/pytest.log"; rc $r
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 r=$?; tail -2 "$OUT/smoke.log"; rc $r
-timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
 r=$?; cat "$OUT/bench.json"; rc $r
 exit 0

@@ -3,7 +3,7 @@
 # producer / consumer launches and the consumer's HBM bytes (FETCH_SIZE, WRITE_SIZE passes).
 #   tools/split_diag.sh <outdir>
 OUT=${1:-gpurun_out/split}
-ARGS="--gram-path split --steps 2 --warmup 1 --no-cpu --no-probe"
+ARGS="--gram-path split --steps 2 --warmup 1 --full --no-cpu --no-probe"
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 300 python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err || exit 1
