@@ -14,7 +14,7 @@
 //   solver 1: K[i+1][j+1] = (K[i][j+1] + K[i+1][j]) (1 + inc/2 + inc^2/12) - K[i][j] (1 - inc^2/12)
 //   solver 0: K[i+1][j+1] = K[i][j+1] + K[i+1][j] + K[i][j] (inc - 1)
 // In DIAG mode with solver 0 the diagonal cells take the solver-1 update, as sigKer_fast.pyx:59 does.
-#include "sig_common.h"
+#include "internal.h"
 #include "gemm.h"
 
 namespace gpsig {
@@ -417,7 +417,7 @@ inline int pde_w64(int J, int REP) {  // W of pde_rep_w's one-pair-per-wave geom
   return 4 * REP;
 }
 inline PdeLp pde_pick_lp(int IC, int J, int REP, int DP) {
-  static const int force = [] { const char *e = getenv("GPSIG_PDE_LP"); return e ? atoi(e) : 0; }();
+  static const int force = env_int("GPSIG_PDE_LP", 0);
   PdeLp best{64, 0};
   if (force == 64) return best;
   double bc = pde_cost(IC, J, REP, DP, pde_w64(J, REP), 1);
@@ -524,35 +524,19 @@ static int pde_launch_args(PdeArgs a, hipStream_t s) {
   PdeLp lpg{64, 0};
   if (!tile && pair_mode != GPSIG_PAIRS_DIAG && solver == 1 && dyadic <= 2 && d <= 8 && l1 >= 2 && l2 >= 2)
     lpg = pde_pick_lp(l1 - 1, J, 1 << dyadic, DPI);
-  const int G = 64 / lpg.LP;
-  long long nblocks;
-  if (pair_mode == GPSIG_PAIRS_DIAG) {
-    nblocks = (row_end - row_begin + 3) / 4;
-  } else {
-    const int ta0 = row_begin / 4, ta1 = (row_end + 3) / 4;
-    const int ntb = (n2 + G - 1) / G;
-    a.ntb = ntb;
-    a.tiles_a0 = ta0;
-    if (pair_mode == GPSIG_PAIRS_RECT) {
-      nblocks = (long long)(ta1 - ta0) * ntb;
-    } else {
-      const long long k = 4 / G;
-      auto P = [&](long long r) { return r * (long long)ntb - k * r * (r - 1) / 2; };
-      a.tile_base = P(ta0);
-      nblocks = P(ta1) - a.tile_base;
-    }
-  }
+  PairTiles t;
+  const int trc = pair_tiles(pair_mode, row_begin, row_end, n2, 64 / lpg.LP, &t);
+  a.ntb = t.ntb;
+  a.tiles_a0 = t.tiles_a0;
+  a.tile_base = t.tile_base;
+  const long long nblocks = t.nblocks;
   if (nblocks <= 0) return GPSIG_OK;
-  if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
+  if (trc) return trc;
   using T = double;  // fp64 solution grid (the reference's float64), fp32 increments (as the CUDA op, .cu:27)
   if (tile) return pde_w<T, 0>(a, nblocks, J, lpg, s);
-  switch (d <= 8 ? d : (d <= 16 ? 16 : 0)) {
-#define CASE(v) \
-  case v: return pde_w<T, v>(a, nblocks, J, lpg, s);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(16)
-#undef CASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8, 16>(d <= 8 ? d : (d <= 16 ? 16 : 0), [&](auto dp) {
+    return pde_w<T, decltype(dp)::value>(a, nblocks, J, lpg, s);
+  });
 }
 
 int pde_launch(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int dyadic, int solver,
@@ -586,7 +570,6 @@ int increments_launch(const float *X, int n, int l, int d, float *dX, hipStream_
   return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
 
-static size_t al256p(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr size_t PDE_TILE_BYTES = (size_t)1 << 30;  // increment tile of one chunk of x-rows
 
 // x-rows per chunk of the tiled paths (a multiple of 4) and the tile's row length (also the higher-order
@@ -607,9 +590,9 @@ size_t pde_tile_scratch_bytes(int n1, int l1, int n2, int l2, int d, int pair_mo
   long long cols;
   pde_tile_chunk(n1, l1, n2, l2, pair_mode, rows, cols);
   const bool same = pair_mode != GPSIG_PAIRS_RECT;
-  return al256p((size_t)n1 * (l1 - 1) * d * sizeof(float)) +
-         (same ? 0 : al256p((size_t)n2 * (l2 - 1) * d * sizeof(float))) +
-         al256p((size_t)rows * (l1 - 1) * cols * sizeof(float));
+  return align256((size_t)n1 * (l1 - 1) * d * sizeof(float)) +
+         (same ? 0 : align256((size_t)n2 * (l2 - 1) * d * sizeof(float))) +
+         align256((size_t)rows * (l1 - 1) * cols * sizeof(float));
 }
 
 // Increment tiles of chunks of x-rows (one matrix-core GEMM each: dX_chunk dY^T, or per pair for DIAG),
@@ -624,11 +607,11 @@ int pde_tiled_run(PdeArgs a, void *scratch, size_t scratch_bytes, hipStream_t s,
   pde_tile_chunk(n1, l1, n2, l2, pm, rows, cols);
   char *w = static_cast<char *>(scratch);
   float *dX = reinterpret_cast<float *>(w);
-  w += al256p((size_t)n1 * IC * d * sizeof(float));
+  w += align256((size_t)n1 * IC * d * sizeof(float));
   float *dY = dX;
   if (pm == GPSIG_PAIRS_RECT) {
     dY = reinterpret_cast<float *>(w);
-    w += al256p((size_t)n2 * JC * d * sizeof(float));
+    w += align256((size_t)n2 * JC * d * sizeof(float));
   }
   float *T = reinterpret_cast<float *>(w);
   int rc = increments_launch(a.X, n1, l1, d, dX, s);

@@ -33,6 +33,7 @@
 #pragma once
 #include <type_traits>
 
+#include "host.h"
 #include "sig_common.h"
 
 namespace gpsig {
@@ -558,14 +559,8 @@ static int launch_pde_adj(const PdeBwdArgs &a, long long nblocks, hipStream_t s)
 
 template <int DP, int REP, int MODE>
 static int pde_adj_w(const PdeBwdArgs &a, long long nblocks, int W, hipStream_t s) {
-  switch (W) {
-    case 1: return launch_pde_adj<DP, 1, REP, MODE>(a, nblocks, s);
-    case 2: return launch_pde_adj<DP, 2, REP, MODE>(a, nblocks, s);
-    case 4: return launch_pde_adj<DP, 4, REP, MODE>(a, nblocks, s);
-    case 8: return launch_pde_adj<DP, 8, REP, MODE>(a, nblocks, s);
-    case 16: return launch_pde_adj<DP, 16, REP, MODE>(a, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 4, 8, 16>(
+      W, [&](auto w) { return launch_pde_adj<DP, decltype(w)::value, REP, MODE>(a, nblocks, s); });
 }
 
 template <int DP, int MODE>
@@ -573,13 +568,8 @@ static int pde_adj_rep(const PdeBwdArgs &a, long long nblocks, hipStream_t s) {
   const int kd = a.dyadic - (DP == 0 ? a.sub : 0);  // the kernel's refinement (TILE: past the tile's cells)
   const int rep = 1 << kd;
   const int W = pde_bwd_cols(rep * ((a.l2 - 1) << (DP == 0 ? a.sub : 0)), rep);
-  switch (kd) {
-    case 0: return pde_adj_w<DP, 1, MODE>(a, nblocks, W, s);
-    case 1: return pde_adj_w<DP, 2, MODE>(a, nblocks, W, s);
-    case 2: return pde_adj_w<DP, 4, MODE>(a, nblocks, W, s);
-    case 3: return pde_adj_w<DP, 8, MODE>(a, nblocks, W, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<0, 1, 2, 3>(
+      kd, [&](auto k) { return pde_adj_w<DP, (1 << decltype(k)::value), MODE>(a, nblocks, W, s); });
 }
 
 // one channel count (pde_bwd_inst.hip, one unit per DP); mode as pde_adj_kernel's MODE

@@ -1,5 +1,6 @@
 // gpsig_amd -- C ABI of the Goursat-PDE gradient (kernels in pde_bwd.h, one instantiation unit per
 // channel count: pde_bwd_inst.hip).
+#include "internal.h"
 #include "pde_bwd.h"
 #include "gemm.h"
 
@@ -7,12 +8,10 @@ namespace gpsig {
 #define DECL(v) extern template int pde_bwd_launch_dp<v>(const PdeBwdArgs &, long long, int, hipStream_t);
 DECL(0) DECL(1) DECL(2) DECL(3) DECL(4) DECL(5) DECL(6) DECL(7) DECL(8) DECL(16)
 #undef DECL
-int increments_launch(const float *X, int n, int l, int d, float *dX, hipStream_t s);
 
 // The adjoint on increment tiles: channel counts past the instantiations, dyadic orders past 3
 bool pde_bwd_tiled(int d, int dyadic) { return d > 16 || dyadic > 3; }
 
-static size_t al256b(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr size_t PDE_BWD_TILE_BYTES = (size_t)1 << 30;  // increment tile (and as much adjoint tile) of a chunk
 
 struct PdeBwdPlan {
@@ -29,18 +28,18 @@ static PdeBwdPlan pde_bwd_plan(int n1, int l1, int n2, int l2, int d, int pair_m
   if (r > ((n1 + 3) / 4) * 4) r = ((n1 + 3) / 4) * 4;
   p.rows = (int)r;
   const bool rect = pair_mode == GPSIG_PAIRS_RECT;
-  p.dx = al256b((size_t)n1 * IC * d * sizeof(float));
-  p.dy = rect ? al256b((size_t)n2 * JC * d * sizeof(float)) : 0;
+  p.dx = align256((size_t)n1 * IC * d * sizeof(float));
+  p.dy = rect ? align256((size_t)n2 * JC * d * sizeof(float)) : 0;
   p.gdx = p.dx;
   p.gdy = p.dy;
-  p.inc = al256b((size_t)r * IC * p.cols * sizeof(float));
+  p.inc = align256((size_t)r * IC * p.cols * sizeof(float));
   p.gt = p.inc;
   // split-K partials of the two adjoint contractions of a full chunk (gdX: R x d, K = cols; gdY: cols x d,
   // K = R); gemm_f32 clamps any split to this capacity
   if (rect) {
     const size_t pr = gemm_splitk_bytes((int)(r * IC), d, (int)p.cols);
     const size_t pc = gemm_splitk_bytes((int)p.cols, d, (int)(r * IC));
-    p.part = al256b(pr > pc ? pr : pc);
+    p.part = align256(pr > pc ? pr : pc);
   }
   return p;
 }
@@ -169,12 +168,10 @@ static int pde_adj_impl(int mode, const float *X, int n1, int l1, const float *Y
                         int solver, int pair_mode, int row_begin, int row_end, const float *gout, float *gX, float *gY,
                         float *out, void *workspace, size_t workspace_bytes, hipStream_t s, void *scratch = nullptr,
                         size_t scratch_bytes = 0) {
-  if (!X || !Y || n1 <= 0 || n2 <= 0 || d <= 0 || l1 < 2 || l2 < 2) return GPSIG_EINVAL;
+  if (check_pair_args(X, Y, n1, l1, n2, l2, d, 2, pair_mode, row_begin, row_end, true)) return GPSIG_EINVAL;
+  if (pair_mode == GPSIG_PAIRS_UPPER) return GPSIG_EINVAL;  // the adjoint has no UPPER mode
   if (mode == 1 ? !out : (!gout || !gX)) return GPSIG_EINVAL;
   if (dyadic < 0 || dyadic > 8 || (solver != 0 && solver != 1)) return GPSIG_EINVAL;
-  if (pair_mode != GPSIG_PAIRS_RECT && pair_mode != GPSIG_PAIRS_DIAG) return GPSIG_EINVAL;
-  if (row_begin < 0 || row_end > n1 || row_begin > row_end) return GPSIG_EINVAL;
-  if (pair_mode == GPSIG_PAIRS_DIAG && (n1 != n2 || l1 != l2 || X != Y)) return GPSIG_EINVAL;
   if (mode != 1 && pair_mode == GPSIG_PAIRS_RECT && !gY) return GPSIG_EINVAL;
   if (row_end == row_begin) return GPSIG_OK;
   const int rows = row_end - row_begin;
@@ -197,6 +194,7 @@ static int pde_adj_impl(int mode, const float *X, int n1, int l1, const float *Y
   const int wc = pair_mode == GPSIG_PAIRS_RECT && mode != 1 ? pde_layout(l1, l2, dyadic).W >> dyadic : 0;
   while (wpb > 1 && (size_t)wpb * pde_lds_wave_doubles(l1 - 1, dp, wc) * sizeof(double) > 160 * 1024) wpb /= 2;
   a.wpb = wpb;
+  // not pair_tiles: wpb (not 4) rows per workgroup, one y-sequence per tile, no UPPER mode
   long long nblocks;
   if (pair_mode == GPSIG_PAIRS_DIAG) {
     nblocks = (rows + wpb - 1) / wpb;
@@ -207,13 +205,8 @@ static int pde_adj_impl(int mode, const float *X, int n1, int l1, const float *Y
     nblocks = (long long)(ta1 - ta0) * n2;
   }
   if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
-  switch (dp) {
-#define CASE(v) \
-  case v: return pde_bwd_launch_dp<v>(a, nblocks, mode, s);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(16)
-#undef CASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8, 16>(
+      dp, [&](auto v) { return pde_bwd_launch_dp<decltype(v)::value>(a, nblocks, mode, s); });
 }
 
 extern "C" int gpsig_pde_vjp_ex(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int dyadic,

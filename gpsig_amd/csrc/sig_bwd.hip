@@ -1,39 +1,25 @@
-// gpsig_amd -- extern "C" entry of the first-order Gram VJP (include/gpsig_amd.h, gpsig_sig_gram_vjp):
-// argument checks, feature records, tile counts, dispatch to the per-(DP, M) instantiations of
-// sig_bwd_kernel (sig_bwd.h, sig_bwd_inst.hip).
+// gpsig_amd -- extern "C" entries of the Gram VJPs (include/gpsig_amd.h: gpsig_sig_gram_vjp,
+// gpsig_sig_gram_vjp_ho and their workspace queries): argument checks, the workspace plan, feature records,
+// tile counts, dispatch to the per-(DP, M) instantiations of sig_bwd_kernel / sig_bwd_pk_kernel (sig_bwd.h,
+// sig_bwd_pk.h, sig_bwd_inst.hip) or to the point-weight-tile VJPs (sig_bwd_wide.hip).  Cross-unit
+// declarations: internal.h; alignment, carving, knobs, dispatch: host.h.
+#include "internal.h"
 #include "sig_bwd_pk.h"
 
 namespace gpsig {
-int features(const float *X, int n, int l, int d, int DP, float *F, hipStream_t s);
-size_t sig_bwd_wide_workspace(int n1, int l1, int n2, int l2, int d);
-int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *workspace, size_t workspace_bytes,
-                 hipStream_t s, int order = 1);
-bool ho_bwd_supported(int l2, int order, int M, int seed);
-size_t ho_bwd_slab_bytes(int l2, int order, int M);
 // channel counts past the VJP's instantiations: the wide-channel VJP (point-weight tiles + GEMMs; slower
 // than the register form at few channels: d = 5 69.7 vs 31.8 ms fwd+bwd at N = 1024, L = 100).
 // GPSIG_VJP_FIXED_MAX lowers the crossover for A/B runs.
 static int vjp_fixed_max() {
-  static const int v = [] {
-    const char *e = getenv("GPSIG_VJP_FIXED_MAX");
-    const int x = e ? atoi(e) : 16;
-    return x < 16 ? (x < 0 ? 0 : x) : 16;
-  }();
+  static const int v = clamp_int(env_int("GPSIG_VJP_FIXED_MAX", 16), 0, 16);
   return v;
 }
 static bool bwd_wide(int d) { return d > vjp_fixed_max(); }
-template <int DP, int M>
-int sig_bwd_launch_dpm(const BwdArgs &a, int seed, long long nblocks, hipStream_t s);
-template <int DP, int M>
-int sig_bwd_pk_launch_dpm(const BwdArgs &a, int seed, BwdGeo geo, long long nblocks, hipStream_t s);
 
 // The packed column-pair VJP (sig_bwd_pk.h) for the difference seeds in one column block; GPSIG_BWD_PK=0
 // keeps sig_bwd_kernel everywhere (A/B runs)
 static bool bwd_pk_enabled() {
-  static const bool v = [] {
-    const char *e = getenv("GPSIG_BWD_PK");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_int("GPSIG_BWD_PK", 1) != 0;
   return v;
 }
 // Measured (tools/kbench_vjp.hip, N = 1024, D = 5, M = 5, saved state; profiles/r6_vjp_ab.txt): at the same
@@ -46,35 +32,6 @@ static BwdGeo bwd_pk_geo(int l2, int DP, int M, int seed) {
   if (old.LP == 20) return {0, 0};
   return bwd_pk_geometry(l2, DP, M, seed == SEED_RBF_DIFF);
 }
-template <int DP>
-static int bwd_pk_dp(const BwdArgs &a, int seed, BwdGeo geo, long long nblocks, hipStream_t s) {
-  switch (a.M) {
-    case 1: return sig_bwd_pk_launch_dpm<DP, 1>(a, seed, geo, nblocks, s);
-    case 2: return sig_bwd_pk_launch_dpm<DP, 2>(a, seed, geo, nblocks, s);
-    case 3: return sig_bwd_pk_launch_dpm<DP, 3>(a, seed, geo, nblocks, s);
-    case 4: return sig_bwd_pk_launch_dpm<DP, 4>(a, seed, geo, nblocks, s);
-    case 5: return sig_bwd_pk_launch_dpm<DP, 5>(a, seed, geo, nblocks, s);
-    case 6: return sig_bwd_pk_launch_dpm<DP, 6>(a, seed, geo, nblocks, s);
-    case 7: return sig_bwd_pk_launch_dpm<DP, 7>(a, seed, geo, nblocks, s);
-    case 8: return sig_bwd_pk_launch_dpm<DP, 8>(a, seed, geo, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
-}
-
-template <int DP>
-static int bwd_dp(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
-  switch (a.M) {
-    case 1: return sig_bwd_launch_dpm<DP, 1>(a, seed, nblocks, s);
-    case 2: return sig_bwd_launch_dpm<DP, 2>(a, seed, nblocks, s);
-    case 3: return sig_bwd_launch_dpm<DP, 3>(a, seed, nblocks, s);
-    case 4: return sig_bwd_launch_dpm<DP, 4>(a, seed, nblocks, s);
-    case 5: return sig_bwd_launch_dpm<DP, 5>(a, seed, nblocks, s);
-    case 6: return sig_bwd_launch_dpm<DP, 6>(a, seed, nblocks, s);
-    case 7: return sig_bwd_launch_dpm<DP, 7>(a, seed, nblocks, s);
-    case 8: return sig_bwd_launch_dpm<DP, 8>(a, seed, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
-}
 
 // channel padding of the VJP instantiations (never wider than the forward's workspace padding)
 static int bwd_pad(int d) {
@@ -84,7 +41,12 @@ static int bwd_pad(int d) {
   return 0;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int vjp_seed(int base_kind, bool difference) {
+  if (base_kind == GPSIG_BASE_RBF) return difference ? SEED_RBF_DIFF : SEED_RBF_POINT;
+  if (base_kind == GPSIG_BASE_LINEAR) return difference ? SEED_LIN_DIFF : SEED_LIN_POINT;
+  return -1;
+}
+
 static constexpr size_t GSC_BYTES = GSCALE_SLOTS * 9 * sizeof(float);  // dscale partials (M <= 8)
 
 // gscale[m] += sum of the GSCALE_SLOTS partial sums of level m
@@ -96,16 +58,67 @@ __global__ void gscale_reduce_kernel(const float *__restrict__ slots, int levels
   gscale[m] += s;
 }
 
-// The VJPs with point-weight tiles and emission GEMMs (sig_bwd_wide.hip): order 1 at wide channel counts,
-// and every order > 1
-static int tile_vjp(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int num_levels, int order,
-                    int seed, int pair_mode, int row_begin, int row_end, const float *gout, int gout_levels,
-                    const float *rs1, const float *rs2, const float *scale, float jitter, float *gX, float *gY,
-                    float *grs1, float *grs2, float *gscale, const float *state, void *workspace,
-                    size_t workspace_bytes, hipStream_t s) {
+// The route of one Gram VJP call and its workspace, in carve order.
+//   register route (order 1 up to vjp_fixed_max() channels): the feature records of X and of Y (none when Y
+//     is X), the column-block scratch of one launch chunk (sequences past one block), the dscale partials;
+//   tile route (sig_bwd_wide.hip: order 1 at wide channel counts, every order > 1): the dscale partials, the
+//     tile VJP's own workspace (any pair mode), the 8-wave higher-order VJP's global slabs (past 509 points).
+struct VjpPlan {
+  bool tile;
+  int DP;  // register route: channel padding, kernel (packed or not), geometry, column blocks
+  bool pk;
+  BwdGeo geo;
+  int nblk;
+  long long scr_stride;
+  size_t fx, fy, scr, gsc, wide, slab;                     // region bytes
+  size_t o_fy, o_scr, o_gsc, o_wide, o_slab, total;        // offsets
+};
+// false: no kernel for the channel count / geometry
+static bool vjp_plan(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int seed, bool difference,
+                     bool same, VjpPlan *p) {
+  *p = VjpPlan{};
+  p->tile = order > 1 || bwd_wide(d);
+  p->gsc = GSC_BYTES;
+  Carver c;
+  if (p->tile) {
+    p->wide = sig_bwd_wide_workspace(n1, l1, n2, l2, d);
+    p->slab = order > 1 ? ho_bwd_slab_bytes(l2, order, num_levels) : 0;
+    p->o_gsc = c.take(p->gsc);
+    p->o_wide = c.take(p->wide);
+    p->o_slab = c.take(p->slab);
+  } else {
+    p->DP = bwd_pad(d);
+    if (p->DP == 0) return false;
+    const BwdGeo pkgeo = bwd_pk_geo(l2, p->DP, num_levels, seed);
+    p->pk = pkgeo.W != 0;
+    p->geo = p->pk ? pkgeo : bwd_geometry(l2, p->DP, num_levels);
+    if (p->geo.W == 0) return false;
+    p->nblk = p->pk ? 1 : bwd_blocks(l2, difference, p->geo);
+    p->scr_stride = bwd_scratch_floats(difference ? l1 - 1 : l1, num_levels, p->geo.W, p->nblk);
+    p->fx = align256((size_t)n1 * l1 * feat_stride(p->DP) * sizeof(float));
+    p->fy = same ? 0 : align256((size_t)n2 * l2 * feat_stride(p->DP) * sizeof(float));
+    p->scr = (size_t)p->scr_stride * 4 * BWD_CHUNK_BLOCKS * sizeof(float);
+    c.take(p->fx);
+    p->o_fy = c.take(p->fy);
+    p->o_scr = c.take(p->scr);
+    p->o_gsc = c.take(p->gsc);
+  }
+  p->total = c.total();
+  return true;
+}
+
+// Both routes: seed < 0 and the supported ranges are the caller's checks.
+static int vjp_run(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int num_levels, int order,
+                   int seed, bool difference, int pair_mode, int row_begin, int row_end, const float *gout,
+                   int gout_levels, const float *rs1, const float *rs2, const float *scale, float jitter, float *gX,
+                   float *gY, float *grs1, float *grs2, float *gscale, const float *state, void *workspace,
+                   size_t workspace_bytes, hipStream_t s) {
+  const bool same = (X == Y && n1 == n2 && l1 == l2);
+  VjpPlan pl;
+  if (!vjp_plan(n1, l1, n2, l2, d, num_levels, order, seed, difference, same, &pl)) return GPSIG_EUNSUPPORTED;
   if (row_end == row_begin) return GPSIG_OK;
-  if (!workspace || workspace_bytes < GSC_BYTES + sig_bwd_wide_workspace(n1, l1, n2, l2, d)) return GPSIG_EWORKSPACE;
-  float *gsc_slots = static_cast<float *>(workspace);
+  if (!workspace || workspace_bytes < pl.total) return GPSIG_EWORKSPACE;
+  float *gsc_slots = ws_at(workspace, pl.o_gsc);
   BwdArgs a{};
   a.n1 = n1; a.l1 = l1; a.n2 = n2; a.l2 = l2; a.d = d;
   a.M = num_levels;
@@ -122,24 +135,64 @@ static int tile_vjp(const float *X, int n1, int l1, const float *Y, int n2, int 
   a.gY = pair_mode == GPSIG_PAIRS_RECT ? gY : gX;
   a.grs1 = grs1;
   a.grs2 = pair_mode == GPSIG_PAIRS_RECT ? grs2 : grs1;
-  a.gscale = nullptr;
+  a.state = state;
+  int rc;
+  if (!pl.tile) {
+    float *FX = static_cast<float *>(workspace), *FY = same ? FX : ws_at(workspace, pl.o_fy);
+    if ((rc = features(X, n1, l1, d, pl.DP, FX, s))) return rc;
+    if (!same && (rc = features(Y, n2, l2, d, pl.DP, FY, s))) return rc;
+    a.FX = FX;
+    a.FY = FY;
+  }
   if (gscale && pair_mode != GPSIG_PAIRS_DIAG) {
     if (hipMemsetAsync(gsc_slots, 0, GSC_BYTES, s) != hipSuccess) return GPSIG_ELAUNCH;
     a.gscale = gsc_slots;
   }
-  a.state = state;
-  // the 8-wave higher-order VJP's global slabs (past 509 points) after the wide workspace
-  const size_t wide_b = sig_bwd_wide_workspace(n1, l1, n2, l2, d);
-  const size_t slab_b = order > 1 ? ho_bwd_slab_bytes(l2, order, num_levels) : 0;
-  if (workspace_bytes < GSC_BYTES + wide_b + slab_b) return GPSIG_EWORKSPACE;
-  a.scratch = slab_b ? reinterpret_cast<float *>(static_cast<char *>(workspace) + GSC_BYTES + wide_b) : nullptr;
-  const int rc = sig_bwd_wide(a, X, pair_mode == GPSIG_PAIRS_RECT ? Y : X, seed, static_cast<char *>(workspace) + GSC_BYTES,
-                              wide_b, s, order);
-  if (rc) return rc;
+  if (pl.tile) {
+    // the VJPs with point-weight tiles and emission GEMMs (sig_bwd_wide.hip)
+    a.scratch = pl.slab ? ws_at(workspace, pl.o_slab) : nullptr;
+    if ((rc = sig_bwd_wide(a, X, pair_mode == GPSIG_PAIRS_RECT ? Y : X, seed, ws_at(workspace, pl.o_wide), pl.wide, s,
+                           order)))
+      return rc;
+  } else {
+    a.nblk = pl.nblk;
+    a.scratch = pl.scr_stride ? ws_at(workspace, pl.o_scr) : nullptr;
+    a.scr_stride = pl.scr_stride;
+    PairTiles t;
+    if ((rc = pair_tiles(pair_mode, row_begin, row_end, n2, 64 / pl.geo.LP, &t))) return rc;
+    a.tiles_a0 = t.tiles_a0;
+    a.ntb = t.ntb;
+    a.tile_base = t.tile_base;
+    if (t.nblocks <= 0) return GPSIG_OK;
+    // column-block launches go in chunks of BWD_CHUNK_BLOCKS workgroups (the scratch holds one chunk)
+    const long long chunk = pl.scr_stride ? BWD_CHUNK_BLOCKS : t.nblocks;
+    for (long long c = 0; c < t.nblocks; c += chunk) {
+      a.blk0 = c;
+      const long long nb = t.nblocks - c < chunk ? t.nblocks - c : chunk;
+      rc = dispatch<1, 2, 3, 4, 5, 6, 8, 16>(pl.DP, [&](auto dp) {
+        return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto m) {
+          constexpr int DP = decltype(dp)::value, M = decltype(m)::value;
+          return pl.pk ? sig_bwd_pk_launch_dpm<DP, M>(a, seed, pl.geo, nb, s) : sig_bwd_launch_dpm<DP, M>(a, seed, nb, s);
+        });
+      });
+      if (rc) return rc;
+    }
+  }
   if (a.gscale) {
     hipLaunchKernelGGL(gscale_reduce_kernel, dim3(1), dim3(64), 0, s, gsc_slots, num_levels + 1, gscale);
     if (hipGetLastError() != hipSuccess) return GPSIG_ELAUNCH;
   }
+  return GPSIG_OK;
+}
+
+// the checks gpsig_sig_gram_vjp and gpsig_sig_gram_vjp_ho share
+static int vjp_check(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int num_levels, int lmin,
+                     int pair_mode, int row_begin, int row_end, const float *gout, int gout_levels, const float *rs1,
+                     const float *rs2, float *gX, float *gY) {
+  if (!gout || !gX || num_levels < 1) return GPSIG_EINVAL;
+  if (check_pair_args(X, Y, n1, l1, n2, l2, d, lmin, pair_mode, row_begin, row_end, true, rs1, rs2)) return GPSIG_EINVAL;
+  if (pair_mode == GPSIG_PAIRS_RECT && !gY) return GPSIG_EINVAL;
+  if (pair_mode == GPSIG_PAIRS_DIAG && !gout_levels) return GPSIG_EINVAL;
   return GPSIG_OK;
 }
 
@@ -153,122 +206,27 @@ extern "C" int gpsig_sig_gram_vjp(const float *X, int n1, int l1, const float *Y
                                   const float *scale, float jitter, float *gX, float *gY, float *grs1, float *grs2,
                                   float *gscale, const float *state, void *workspace, size_t workspace_bytes,
                                   gpsig_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!X || !Y || !gout || !gX || n1 <= 0 || n2 <= 0 || d <= 0 || num_levels < 1) return GPSIG_EINVAL;
-  if (l1 < 1 || l2 < 1 || (difference && (l1 < 2 || l2 < 2))) return GPSIG_EINVAL;
-  if (pair_mode < GPSIG_PAIRS_RECT || pair_mode > GPSIG_PAIRS_DIAG) return GPSIG_EINVAL;
-  if (row_begin < 0 || row_end > n1 || row_begin > row_end) return GPSIG_EINVAL;
-  if (pair_mode != GPSIG_PAIRS_RECT && (n1 != n2 || l1 != l2 || X != Y)) return GPSIG_EINVAL;
-  if (pair_mode == GPSIG_PAIRS_RECT && !gY) return GPSIG_EINVAL;
-  if (pair_mode == GPSIG_PAIRS_DIAG && !gout_levels) return GPSIG_EINVAL;
-  if ((rs1 == nullptr) != (rs2 == nullptr)) return GPSIG_EINVAL;
+  if (vjp_check(X, n1, l1, Y, n2, l2, d, num_levels, difference ? 2 : 1, pair_mode, row_begin, row_end, gout,
+                gout_levels, rs1, rs2, gX, gY))
+    return GPSIG_EINVAL;
   if (state && (pair_mode == GPSIG_PAIRS_DIAG || !difference)) return GPSIG_EINVAL;
-  const int seed = base_kind == GPSIG_BASE_RBF ? (difference ? SEED_RBF_DIFF : SEED_RBF_POINT)
-                   : base_kind == GPSIG_BASE_LINEAR ? (difference ? SEED_LIN_DIFF : SEED_LIN_POINT) : -1;
-  const bool wide = bwd_wide(d);
-  const int DP = wide ? 0 : bwd_pad(d);
-  if (seed < 0 || (DP == 0 && !wide) || num_levels > 8) return GPSIG_EUNSUPPORTED;
-  if (wide)
-    return tile_vjp(X, n1, l1, Y, n2, l2, d, num_levels, 1, seed, pair_mode, row_begin, row_end, gout, gout_levels,
-                    rs1, rs2, scale, jitter, gX, gY, grs1, grs2, gscale, state, workspace, workspace_bytes, s);
-  const BwdGeo pkgeo = bwd_pk_geo(l2, DP, num_levels, seed);
-  const bool pk = pkgeo.W != 0;
-  const BwdGeo geo = pk ? pkgeo : bwd_geometry(l2, DP, num_levels);
-  if (geo.W == 0) return GPSIG_EUNSUPPORTED;
-  if (row_end == row_begin) return GPSIG_OK;
-  const int nblk = pk ? 1 : bwd_blocks(l2, difference != 0, geo);
-  const long long scr_stride = bwd_scratch_floats(difference ? l1 - 1 : l1, num_levels, geo.W, nblk);
-
-  const bool same = (X == Y && n1 == n2 && l1 == l2);
-  const size_t fx_b = align256((size_t)n1 * l1 * feat_stride(DP) * sizeof(float));
-  const size_t fy_b = same ? 0 : align256((size_t)n2 * l2 * feat_stride(DP) * sizeof(float));
-  const size_t scr_b = (size_t)scr_stride * 4 * BWD_CHUNK_BLOCKS * sizeof(float);
-  if (!workspace || workspace_bytes < fx_b + fy_b + scr_b + GSC_BYTES) return GPSIG_EWORKSPACE;
-  float *gsc_slots = reinterpret_cast<float *>(static_cast<char *>(workspace) + fx_b + fy_b + scr_b);
-  float *FX = static_cast<float *>(workspace);
-  float *FY = same ? FX : reinterpret_cast<float *>(static_cast<char *>(workspace) + fx_b);
-  int rc = features(X, n1, l1, d, DP, FX, s);
-  if (rc) return rc;
-  if (!same && (rc = features(Y, n2, l2, d, DP, FY, s))) return rc;
-
-  BwdArgs a{};
-  a.FX = FX;
-  a.FY = FY;
-  a.n1 = n1; a.l1 = l1; a.n2 = n2; a.l2 = l2; a.d = d;
-  a.M = num_levels;
-  a.pair_mode = pair_mode;
-  a.row_begin = row_begin;
-  a.row_end = row_end;
-  a.gout = gout;
-  a.gout_levels = gout_levels ? 1 : 0;
-  a.g_ld = n2;
-  a.g_lvl = pair_mode == GPSIG_PAIRS_DIAG ? (long long)n1 : (long long)n1 * n2;
-  a.rs1 = rs1; a.rs2 = rs2; a.scale = scale;
-  a.jitter = jitter;
-  a.gX = gX;
-  a.gY = pair_mode == GPSIG_PAIRS_RECT ? gY : gX;
-  a.grs1 = grs1;
-  a.grs2 = pair_mode == GPSIG_PAIRS_RECT ? grs2 : grs1;
-  a.gscale = nullptr;
-  if (gscale && pair_mode != GPSIG_PAIRS_DIAG) {
-    if (hipMemsetAsync(gsc_slots, 0, GSC_BYTES, s) != hipSuccess) return GPSIG_ELAUNCH;
-    a.gscale = gsc_slots;
-  }
-  a.state = state;
-  a.nblk = nblk;
-  a.scratch = scr_stride ? reinterpret_cast<float *>(static_cast<char *>(workspace) + fx_b + fy_b) : nullptr;
-  a.scr_stride = scr_stride;
-
-  const int G = 64 / geo.LP;
-  long long nblocks;
-  if (pair_mode == GPSIG_PAIRS_DIAG) {
-    nblocks = (row_end - row_begin + 3) / 4;
-  } else {
-    const int ta0 = row_begin / 4, ta1 = (row_end + 3) / 4;
-    const int ntb = (n2 + G - 1) / G;
-    a.tiles_a0 = ta0;
-    a.ntb = ntb;
-    if (pair_mode == GPSIG_PAIRS_RECT) {
-      nblocks = (long long)(ta1 - ta0) * ntb;
-    } else {
-      a.tile_base = upper_prefix_g(ta0, ntb, G);
-      nblocks = upper_prefix_g(ta1, ntb, G) - a.tile_base;
-    }
-  }
-  if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
-  if (nblocks <= 0) return GPSIG_OK;
-  // column-block launches go in chunks of BWD_CHUNK_BLOCKS workgroups (the scratch holds one chunk)
-  const long long chunk = scr_stride ? BWD_CHUNK_BLOCKS : nblocks;
-  for (long long c = 0; c < nblocks; c += chunk) {
-    a.blk0 = c;
-    const long long nb = nblocks - c < chunk ? nblocks - c : chunk;
-    switch (DP) {
-#define CASE(v) \
-  case v: rc = pk ? bwd_pk_dp<v>(a, seed, geo, nb, s) : bwd_dp<v>(a, seed, nb, s); break;
-      CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(8) CASE(16)
-#undef CASE
-      default: return GPSIG_EUNSUPPORTED;
-    }
-    if (rc) return rc;
-  }
-  if (a.gscale) {
-    hipLaunchKernelGGL(gscale_reduce_kernel, dim3(1), dim3(64), 0, s, gsc_slots, num_levels + 1, gscale);
-    if (hipGetLastError() != hipSuccess) return GPSIG_ELAUNCH;
-  }
-  return GPSIG_OK;
+  const int seed = vjp_seed(base_kind, difference != 0);
+  if (seed < 0 || num_levels > 8) return GPSIG_EUNSUPPORTED;
+  return vjp_run(X, n1, l1, Y, n2, l2, d, num_levels, 1, seed, difference != 0, pair_mode, row_begin, row_end, gout,
+                 gout_levels, rs1, rs2, scale, jitter, gX, gY, grs1, grs2, gscale, state, workspace, workspace_bytes,
+                 reinterpret_cast<hipStream_t>(stream));
 }
 
+// The query names no base kind and no X == Y: the largest of the plans those allow.
 extern "C" size_t gpsig_sig_vjp_workspace_bytes(int n1, int l1, int n2, int l2, int d, int num_levels, int difference) {
   if (n1 <= 0 || n2 <= 0 || l1 < 1 || l2 < 1 || d <= 0) return 0;
-  if (bwd_wide(d)) return GSC_BYTES + sig_bwd_wide_workspace(n1, l1, n2, l2, d);
-  const int DP = bwd_pad(d);
-  if (DP == 0 || n1 <= 0 || n2 <= 0 || l1 < 1 || l2 < 1) return 0;
-  const BwdGeo geo = bwd_geometry(l2, DP);
-  const int nblk = bwd_blocks(l2, difference != 0, geo);
-  const long long scr = bwd_scratch_floats(difference ? l1 - 1 : l1, num_levels, geo.W, nblk);
-  return align256((size_t)n1 * l1 * feat_stride(DP) * sizeof(float)) +
-         align256((size_t)n2 * l2 * feat_stride(DP) * sizeof(float)) + (size_t)scr * 4 * BWD_CHUNK_BLOCKS * sizeof(float) +
-         GSC_BYTES;
+  size_t best = 0;
+  for (int base : {GPSIG_BASE_RBF, GPSIG_BASE_LINEAR}) {
+    VjpPlan p;
+    if (!vjp_plan(n1, l1, n2, l2, d, num_levels, 1, vjp_seed(base, difference != 0), difference != 0, false, &p)) continue;
+    best = p.total > best ? p.total : best;
+  }
+  return best;
 }
 
 extern "C" int gpsig_sig_gram_vjp_ho(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d,
@@ -277,30 +235,26 @@ extern "C" int gpsig_sig_gram_vjp_ho(const float *X, int n1, int l1, const float
                                      const float *rs2, const float *scale, float jitter, float *gX, float *gY,
                                      float *grs1, float *grs2, float *gscale, void *workspace,
                                      size_t workspace_bytes, gpsig_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!X || !Y || !gout || !gX || n1 <= 0 || n2 <= 0 || d <= 0 || num_levels < 1 || order < 1) return GPSIG_EINVAL;
-  if (l1 < 2 || l2 < 2) return GPSIG_EINVAL;
-  if (pair_mode < GPSIG_PAIRS_RECT || pair_mode > GPSIG_PAIRS_DIAG) return GPSIG_EINVAL;
-  if (row_begin < 0 || row_end > n1 || row_begin > row_end) return GPSIG_EINVAL;
-  if (pair_mode != GPSIG_PAIRS_RECT && (n1 != n2 || l1 != l2 || X != Y)) return GPSIG_EINVAL;
-  if (pair_mode == GPSIG_PAIRS_RECT && !gY) return GPSIG_EINVAL;
-  if (pair_mode == GPSIG_PAIRS_DIAG && !gout_levels) return GPSIG_EINVAL;
-  if ((rs1 == nullptr) != (rs2 == nullptr)) return GPSIG_EINVAL;
+  if (order < 1 || vjp_check(X, n1, l1, Y, n2, l2, d, num_levels, 2, pair_mode, row_begin, row_end, gout, gout_levels,
+                             rs1, rs2, gX, gY))
+    return GPSIG_EINVAL;
   if (order == 1 || num_levels == 1)  // the first-order recursion
     return gpsig_sig_gram_vjp(X, n1, l1, Y, n2, l2, d, num_levels, base_kind, 1, pair_mode, row_begin, row_end, gout,
                               gout_levels, rs1, rs2, scale, jitter, gX, gY, grs1, grs2, gscale, nullptr, workspace,
                               workspace_bytes, stream);
-  const int seed = base_kind == GPSIG_BASE_RBF ? SEED_RBF_DIFF : base_kind == GPSIG_BASE_LINEAR ? SEED_LIN_DIFF : -1;
+  const int seed = vjp_seed(base_kind, true);
   if (seed < 0 || !ho_bwd_supported(l2, order, num_levels, seed)) return GPSIG_EUNSUPPORTED;
-  return tile_vjp(X, n1, l1, Y, n2, l2, d, num_levels, order, seed, pair_mode, row_begin, row_end, gout, gout_levels,
-                  rs1, rs2, scale, jitter, gX, gY, grs1, grs2, gscale, nullptr, workspace, workspace_bytes, s);
+  return vjp_run(X, n1, l1, Y, n2, l2, d, num_levels, order, seed, true, pair_mode, row_begin, row_end, gout,
+                 gout_levels, rs1, rs2, scale, jitter, gX, gY, grs1, grs2, gscale, nullptr, workspace, workspace_bytes,
+                 reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t gpsig_sig_vjp_ho_workspace_bytes(int n1, int l1, int n2, int l2, int d, int num_levels, int order,
                                                    int base_kind) {
   if (n1 <= 0 || n2 <= 0 || l1 < 2 || l2 < 2 || d <= 0 || order < 1) return 0;
   if (order == 1 || num_levels == 1) return gpsig_sig_vjp_workspace_bytes(n1, l1, n2, l2, d, num_levels, 1);
-  const int seed = base_kind == GPSIG_BASE_RBF ? SEED_RBF_DIFF : base_kind == GPSIG_BASE_LINEAR ? SEED_LIN_DIFF : -1;
+  const int seed = vjp_seed(base_kind, true);
+  VjpPlan p;
   if (seed < 0 || !ho_bwd_supported(l2, order, num_levels, seed)) return 0;
-  return GSC_BYTES + sig_bwd_wide_workspace(n1, l1, n2, l2, d) + ho_bwd_slab_bytes(l2, order, num_levels);
+  return vjp_plan(n1, l1, n2, l2, d, num_levels, order, seed, true, false, &p) ? p.total : 0;
 }

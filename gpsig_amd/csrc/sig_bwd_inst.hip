@@ -1,5 +1,6 @@
 // One (channel count, level count) instantiation of the first-order Gram VJP kernel (sig_bwd.h);
 // compiled once per -DGPSIG_DP=.. -DGPSIG_M=.. so the instantiations build in parallel.
+#include "internal.h"
 #include "sig_bwd_pk.h"
 
 namespace gpsig {

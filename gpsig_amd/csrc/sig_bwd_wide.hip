@@ -2,15 +2,11 @@
 // tile of each chunk, and the emission GEMMs on the matrix cores (gemm.hip):
 //   [gX | rowsum] += W [Y | 1],   [gY | colsum] += W^T [X | 1],   then  g -= rowsum * x  (RBF)
 // (UPPER / DIAG: Y = X, both sides go to gX).
+#include "internal.h"
 #include "sig_bwd_wide.h"
 #include "gemm.h"
 
 namespace gpsig {
-
-template <int M>
-int sig_bwd_wide_launch_m(const BwdArgs &a, int seed, long long nblocks, hipStream_t s);
-bool ho_bwd_supported(int l2, int order, int M, int seed);
-int sig_ho_bwd_launch(const BwdArgs &a, int order, int seed, long long nblocks, hipStream_t s);
 
 // Xa[r][k] = X[r][k] (k < d), Xa[r][d] = 1
 __global__ __launch_bounds__(256) void aug_ones_kernel(const float *__restrict__ X, long long rows, int d,
@@ -33,8 +29,6 @@ __global__ __launch_bounds__(256) void emit_correct_kernel(const float *__restri
   const float *Gr = G + r * (d + 1);
   g[idx] += rbf ? __builtin_fmaf(-Gr[d], X[idx], Gr[k]) : Gr[k];
 }
-
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 DiagTiles diag_tiles_of(int l, int W, int LP) {
   const long long rp = (((long long)(l - 1) + 7) / 8) * 8;
@@ -107,7 +101,6 @@ int wide_diag_tiles(const float *FX, long long sx, int d, int lw, int a0, int np
                      dim3(256), 0, s, rec, sx, d, lw, dt, T);
   return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
-static inline long long up_prefix(long long r, long long ntb, long long k) { return r * ntb - k * r * (r - 1) / 2; }
 
 // point-weight tile budget of one chunk of x-rows
 constexpr size_t WIDE_TILE_BYTES = (size_t)1 << 30;
@@ -130,21 +123,21 @@ static WidePlan wide_plan(int n1, int l1, int n2, int l2, int d, int pair_mode) 
   }
   if (rows > ((n1 + 3) / 4) * 4) rows = ((n1 + 3) / 4) * 4;
   p.rows = (int)rows;
-  p.rec_x = al256((size_t)n1 * wide_rec_floats(d, l1) * sizeof(float));
-  p.rec_y = same ? 0 : al256((size_t)n2 * wide_rec_floats(d, l2) * sizeof(float));
-  p.aug_x = al256((size_t)n1 * l1 * (d + 1) * sizeof(float));
-  p.aug_y = same ? 0 : al256((size_t)n2 * l2 * (d + 1) * sizeof(float));
-  p.gx = al256((size_t)n1 * l1 * (d + 1) * sizeof(float));
-  p.gc = pair_mode == GPSIG_PAIRS_DIAG ? 0 : al256((size_t)n2 * l2 * (d + 1) * sizeof(float));
-  p.tile = al256((size_t)rows * l1 * cols * sizeof(float));
+  p.rec_x = align256((size_t)n1 * wide_rec_floats(d, l1) * sizeof(float));
+  p.rec_y = same ? 0 : align256((size_t)n2 * wide_rec_floats(d, l2) * sizeof(float));
+  p.aug_x = align256((size_t)n1 * l1 * (d + 1) * sizeof(float));
+  p.aug_y = same ? 0 : align256((size_t)n2 * l2 * (d + 1) * sizeof(float));
+  p.gx = align256((size_t)n1 * l1 * (d + 1) * sizeof(float));
+  p.gc = pair_mode == GPSIG_PAIRS_DIAG ? 0 : align256((size_t)n2 * l2 * (d + 1) * sizeof(float));
+  p.tile = align256((size_t)rows * l1 * cols * sizeof(float));
   // split-K partials of the row-side (rows * l1 x (d + 1), K = cols) and column-side (cols x (d + 1),
   // K = rows * l1) products of a full chunk; gemm_f32 clamps any split to this capacity
   if (pair_mode != GPSIG_PAIRS_DIAG) {
     const size_t pr = gemm_splitk_bytes((int)(rows * l1), d + 1, (int)cols);
     const size_t pc = gemm_splitk_bytes((int)cols, d + 1, (int)(rows * l1));
-    p.part = al256(pr > pc ? pr : pc);
+    p.part = align256(pr > pc ? pr : pc);
   } else if (dg.W > 0) {
-    p.dtile = al256((size_t)rows * diag_tiles_of(l1, dg.W, dg.LP).pair * sizeof(float));
+    p.dtile = align256((size_t)rows * diag_tiles_of(l1, dg.W, dg.LP).pair * sizeof(float));
   }
   return p;
 }
@@ -206,7 +199,6 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
   if (order == 1) a.scratch = nullptr;  // order > 1: the caller's slab region of the 8-wave split VJP (or null)
   a.scr_stride = 0;
   const int G = 64 / geo.LP;
-  const int ntb = (n2 + G - 1) / G;
   const int rb0 = a.row_begin, rb1 = a.row_end;
   const bool rbf = seed == SEED_RBF_DIFF || seed == SEED_RBF_POINT;
   for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += pl.rows) {
@@ -218,11 +210,12 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
     c.row_end = r1;
     c.blk0 = 0;
     c.tile_a0 = r0;
-    long long nblocks;
+    // tiles from the chunk's first 4-aligned row r0 (DIAG: its pairs from c0)
+    PairTiles pt;
+    const int trc = pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, G, &pt);
+    const long long nblocks = pt.nblocks;
     long long tcols;  // tile row length (floats)
     if (pm == GPSIG_PAIRS_DIAG) {
-      c.row_begin = c0;
-      nblocks = (r1 - c0 + 3) / 4;
       // DIAG enumerates a = row_begin + 4 blk + wave: keep the tile rows relative to c0
       c.tile_a0 = c0;
       c.tile_b0 = 0;
@@ -239,41 +232,25 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
         c.dt_ld = dt.ld;
       }
     } else {
-      const int ta0 = r0 / 4, ta1 = (r1 + 3) / 4;
-      c.tiles_a0 = ta0;
-      c.ntb = ntb;
+      c.tiles_a0 = pt.tiles_a0;
+      c.ntb = pt.ntb;
+      c.tile_base = pt.tile_base;
       c.tile_b0 = pm == GPSIG_PAIRS_UPPER ? r0 : 0;
       tcols = (long long)(n2 - c.tile_b0) * l2;
       c.tile_as = (long long)l1 * tcols;
       c.tile_ld = tcols;
-      if (pm == GPSIG_PAIRS_RECT) {
-        nblocks = (long long)(ta1 - ta0) * ntb;
-      } else {
-        const int k = 4 / G;
-        c.tile_base = up_prefix(ta0, ntb, k);
-        nblocks = up_prefix(ta1, ntb, k) - c.tile_base;
-      }
       // pairs b < a of the chunk's own rows (UPPER) and rows before the window (c0 > r0) are not
       // evaluated: their weights are zeros
       if ((pm == GPSIG_PAIRS_UPPER || c0 > r0) && hipMemsetAsync(T, 0, (size_t)nr * l1 * tcols * sizeof(float), s) != hipSuccess)
         return GPSIG_ELAUNCH;
     }
-    if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
+    if (trc) return trc;
     if (nblocks > 0 && order > 1) {
       if ((rc = sig_ho_bwd_launch(c, order, seed, nblocks, s))) return rc;
     } else if (nblocks > 0) {
-      switch (a.M) {
-        case 1: rc = sig_bwd_wide_launch_m<1>(c, seed, nblocks, s); break;
-        case 2: rc = sig_bwd_wide_launch_m<2>(c, seed, nblocks, s); break;
-        case 3: rc = sig_bwd_wide_launch_m<3>(c, seed, nblocks, s); break;
-        case 4: rc = sig_bwd_wide_launch_m<4>(c, seed, nblocks, s); break;
-        case 5: rc = sig_bwd_wide_launch_m<5>(c, seed, nblocks, s); break;
-        case 6: rc = sig_bwd_wide_launch_m<6>(c, seed, nblocks, s); break;
-        case 7: rc = sig_bwd_wide_launch_m<7>(c, seed, nblocks, s); break;
-        case 8: rc = sig_bwd_wide_launch_m<8>(c, seed, nblocks, s); break;
-        default: return GPSIG_EUNSUPPORTED;
-      }
-      if (rc) return rc;
+      if ((rc = dispatch<1, 2, 3, 4, 5, 6, 7, 8>(
+               a.M, [&](auto m) { return sig_bwd_wide_launch_m<decltype(m)::value>(c, seed, nblocks, s); })))
+        return rc;
     }
     const int D1 = d + 1;
     if (pm == GPSIG_PAIRS_DIAG) {

@@ -1,5 +1,6 @@
 // One level-count instantiation of the wide-channel Gram VJP kernel (sig_bwd_wide.h); compiled once per
 // -DGPSIG_M=.. so the instantiations build in parallel.
+#include "internal.h"
 #include "sig_bwd_wide.h"
 #if !defined(GPSIG_M)
 #error "GPSIG_M must be defined"

@@ -542,8 +542,6 @@ int fo_geo(const SigArgs &a, long long nblocks, hipStream_t s) {
 
 // sig_fo_launch_dpm<DP, M> (the per-seed dispatch) is defined only in sig_fo_inst.hip, one translation
 // unit per (channel count, level count): a definition visible here would make every includer instantiate
-// (and embed device code for) all of them.
-template <int DP, int M>
-int sig_fo_launch_dpm(const SigArgs &a, int seed, long long nblocks, hipStream_t s);
+// (and embed device code for) all of them.  Declared in internal.h.
 
 }  // namespace gpsig

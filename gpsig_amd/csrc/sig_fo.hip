@@ -10,6 +10,7 @@
 // column sums C_m(j) = sum_{i'<i} R_m(i', j), so per pair the state is (M x W) registers per lane
 // and the only cross-lane traffic is one DPP scan per level per row.  K_m = sum_j C_m(j) at the end.
 //
+#include "internal.h"
 #include "sig_fo.h"
 
 namespace gpsig {
@@ -51,31 +52,8 @@ static int launch_features(const float *X, int n, int l, int d, float *F, hipStr
 }
 
 int features(const float *X, int n, int l, int d, int DP, float *F, hipStream_t s) {
-  switch (DP) {
-#define CASE(v) \
-  case v: return launch_features<v>(X, n, l, d, F, s);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
-}
-
-template <int DP, int M>
-int sig_fo_launch_dpm(const SigArgs &a, int seed, long long nblocks, hipStream_t s);
-
-template <int DP>
-static int fo_dp(const SigArgs &a, int seed, long long nblocks, hipStream_t s) {
-  switch (a.M) {
-    case 1: return sig_fo_launch_dpm<DP, 1>(a, seed, nblocks, s);
-    case 2: return sig_fo_launch_dpm<DP, 2>(a, seed, nblocks, s);
-    case 3: return sig_fo_launch_dpm<DP, 3>(a, seed, nblocks, s);
-    case 4: return sig_fo_launch_dpm<DP, 4>(a, seed, nblocks, s);
-    case 5: return sig_fo_launch_dpm<DP, 5>(a, seed, nblocks, s);
-    case 6: return sig_fo_launch_dpm<DP, 6>(a, seed, nblocks, s);
-    case 7: return sig_fo_launch_dpm<DP, 7>(a, seed, nblocks, s);
-    case 8: return sig_fo_launch_dpm<DP, 8>(a, seed, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8, 16, 32, 64>(
+      DP, [&](auto dp) { return launch_features<decltype(dp)::value>(X, n, l, d, F, s); });
 }
 
 int sig_fo_launch(const SigArgs &a0, int DP, int seed, long long nblocks, hipStream_t s) {
@@ -83,13 +61,11 @@ int sig_fo_launch(const SigArgs &a0, int DP, int seed, long long nblocks, hipStr
   if (g.W == 0) return GPSIG_EUNSUPPORTED;
   SigArgs a = a0;
   a.nblk = fo_blocks(a0.l2, seed == SEED_RBF_DIFF || seed == SEED_LIN_DIFF, g);
-  switch (DP) {
-#define CASE(v) \
-  case v: return fo_dp<v>(a, seed, nblocks, s);
-    CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(8)
-#undef CASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<0, 1, 2, 3, 4, 5, 6, 8>(DP, [&](auto dp) {
+    return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto m) {
+      return sig_fo_launch_dpm<decltype(dp)::value, decltype(m)::value>(a, seed, nblocks, s);
+    });
+  });
 }
 
 int fo_lanes_per_pair(int l2, int DP, int M, bool mf, int seed, bool split) {

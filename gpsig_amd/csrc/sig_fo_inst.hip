@@ -1,5 +1,6 @@
 // gpsig_amd -- explicit instantiation unit: the first-order kernels for one (channel count, level
 // count).  Compiled once per (GPSIG_DP, GPSIG_M) by gpsig_amd/csrc/Makefile.
+#include "internal.h"
 #include "sig_fo.h"
 #if !defined(GPSIG_DP) || !defined(GPSIG_M)
 #error "GPSIG_DP and GPSIG_M must be defined"

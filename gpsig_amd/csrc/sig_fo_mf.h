@@ -25,7 +25,7 @@
 //     e_ij = -|x_i - y_j|^2 / 2,  e_{i+1,j} = e_ij + p_ij,  e_{0,j+1} = e_0j + q_0j   (e_00 exact)
 // k = exp(e) and expm1(q) by the exp-free recurrences between anchor rows, re-anchored from e and Q.
 #pragma once
-#include <stdlib.h>
+#include "host.h"
 #include "sig_common.h"
 
 namespace gpsig {
@@ -90,8 +90,8 @@ struct MfGeo {
 };
 inline MfGeo mf_geo(int d, int l2) {
   if (mf_w(l2) == 0) return {0, 0};
-  static const int parts = [] { const char *e = getenv("GPSIG_MF_PARTS"); return e ? atoi(e) : 2; }();
-  static const bool four = [] { const char *e = getenv("GPSIG_MF_NW"); return e && e[0] == '4'; }();
+  static const int parts = env_int("GPSIG_MF_PARTS", 2);
+  static const bool four = env_char("GPSIG_MF_NW") == '4';
   for (int nw : {8, 4}) {
     if (nw == 8 && four) continue;
     if (parts == 3 && mf_lds_bytes(d, l2, nw, 3) <= MF_LDS_MAX) return {nw, 3};

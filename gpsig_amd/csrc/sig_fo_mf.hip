@@ -1,5 +1,6 @@
 // gpsig_amd -- host side of the matrix-core wide-channel Gram (sig_fo_mf.h): the GEMM operand records and the
 // pair-tile launch.
+#include "internal.h"
 #include "sig_fo_mf.h"
 
 namespace gpsig {
@@ -167,6 +168,7 @@ int sig_fo_mf(const SigArgs &a0, int d, int seed, float *scratch, hipStream_t s)
   if (m.nblk > 1 && a0.M > 1 && !scratch) return GPSIG_EWORKSPACE;
   const int xb = mf_waves(d, a0.l2) * MF_G;  // x-sequences per workgroup
   const int t0 = a0.row_begin / xb, t1 = (a0.row_end + xb - 1) / xb;
+  // not pair_tiles: xb (not 4) x-sequences per workgroup against single y-sequences, tile_base also for RECT
   long long nblocks;
   if (a0.pair_mode == GPSIG_PAIRS_UPPER) {
     auto P = [&](long long r) { return r * a0.n2 - (long long)xb * r * (r - 1) / 2; };
@@ -178,20 +180,9 @@ int sig_fo_mf(const SigArgs &a0, int d, int seed, float *scratch, hipStream_t s)
   }
   if (nblocks <= 0) return GPSIG_OK;
   if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
-  switch (a0.M) {
-    case 1: return sig_fo_mf_launch_m<1>(m, seed, nblocks, s);
-    case 2: return sig_fo_mf_launch_m<2>(m, seed, nblocks, s);
-    case 3: return sig_fo_mf_launch_m<3>(m, seed, nblocks, s);
-    case 4: return sig_fo_mf_launch_m<4>(m, seed, nblocks, s);
-    case 5: return sig_fo_mf_launch_m<5>(m, seed, nblocks, s);
-    case 6: return sig_fo_mf_launch_m<6>(m, seed, nblocks, s);
-    case 7: return sig_fo_mf_launch_m<7>(m, seed, nblocks, s);
-    case 8: return sig_fo_mf_launch_m<8>(m, seed, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(
+      a0.M, [&](auto lv) { return sig_fo_mf_launch_m<decltype(lv)::value>(m, seed, nblocks, s); });
 }
-
-int sig_fo_mf_cells_launch(const MfArgs &a, long long nblocks, hipStream_t s);
 
 // The RBF difference-seed cells of the pairs of rows [row_begin, row_end) (pair_mode RECT / UPPER: against every
 // / every later y-sequence; DIAG: (a, a)) into the higher-order recursion's tile: cell (i, j) of pair (a, b) at

@@ -1,5 +1,6 @@
 // gpsig_amd -- instantiations of the matrix-core wide-channel Gram (sig_fo_mf.h) for one level count
 // (GPSIG_M): columns per lane 4 / 8 / 10, RBF and linear difference seeds, with and without saved state.
+#include "internal.h"
 #include "sig_fo_mf.h"
 
 #ifndef GPSIG_M
@@ -42,21 +43,14 @@ static int mf_launch_nw(const MfArgs &a, long long nblocks, hipStream_t s) {
 }
 template <int W, int M, int SEED>
 static int mf_launch_w(const MfArgs &a, long long nblocks, hipStream_t s) {
-  switch (mf_waves(a.d, a.p.l2)) {
-    case 8: return mf_launch_nw<8, W, M, SEED>(a, nblocks, s);
-    case 4: return mf_launch_nw<4, W, M, SEED>(a, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<8, 4>(mf_waves(a.d, a.p.l2),
+                        [&](auto nw) { return mf_launch_nw<decltype(nw)::value, W, M, SEED>(a, nblocks, s); });
 }
 
 template <int M, int SEED>
 static int mf_launch_seed(const MfArgs &a, long long nblocks, hipStream_t s) {
-  switch (mf_w(a.p.l2)) {
-    case 4: return mf_launch_w<4, M, SEED>(a, nblocks, s);
-    case 8: return mf_launch_w<8, M, SEED>(a, nblocks, s);
-    case 10: return mf_launch_w<10, M, SEED>(a, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<4, 8, 10>(mf_w(a.p.l2),
+                            [&](auto w) { return mf_launch_w<decltype(w)::value, M, SEED>(a, nblocks, s); });
 }
 
 template <>
@@ -81,19 +75,16 @@ static int mf_cells_launch(const MfArgs &a, long long nblocks, hipStream_t s) {
 }
 template <int NW>
 static int mf_cells_nw(const MfArgs &a, long long nblocks, hipStream_t s) {
-  switch (mf_w(a.p.l2)) {
-    case 4: return mf_cells_launch<NW, 4, false>(a, nblocks, s);
-    case 8: return a.nblk > 1 ? mf_cells_launch<NW, 8, true>(a, nblocks, s) : mf_cells_launch<NW, 8, false>(a, nblocks, s);
-    case 10: return mf_cells_launch<NW, 10, false>(a, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<4, 8, 10>(mf_w(a.p.l2), [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if constexpr (W == 8)
+      if (a.nblk > 1) return mf_cells_launch<NW, 8, true>(a, nblocks, s);
+    return mf_cells_launch<NW, W, false>(a, nblocks, s);
+  });
 }
 int sig_fo_mf_cells_launch(const MfArgs &a, long long nblocks, hipStream_t s) {
-  switch (mf_waves(a.d, a.p.l2)) {
-    case 8: return mf_cells_nw<8>(a, nblocks, s);
-    case 4: return mf_cells_nw<4>(a, nblocks, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<8, 4>(mf_waves(a.d, a.p.l2),
+                        [&](auto nw) { return mf_cells_nw<decltype(nw)::value>(a, nblocks, s); });
 }
 #endif
 

@@ -14,9 +14,7 @@
 // column is the halo point), left to right over all rows; the exclusive column scans of a block add the
 // carry of the blocks to its left: per row, one float per scanned quantity (S00 and Sa[1..dn-1] of each
 // level), kept in this wave's LDS slab.
-#include <stdlib.h>
-
-#include "sig_common.h"
+#include "internal.h"
 #include "gemm.h"
 
 namespace gpsig {
@@ -383,12 +381,8 @@ static size_t ho_carry_bytes(int l1, int order, int M, int nblk) {
 constexpr size_t HO_MAX_CARRY_BYTES = 160 * 1024;
 
 // the split form (one pair per workgroup, column blocks side by side) for calls with few pairs: below about
-// two waves per SIMD the plain kernel leaves the chip idle (GPSIG_HO_SPLIT=0 keeps the plain kernel)
+// two waves per SIMD the plain kernel leaves the chip idle (GPSIG_HO_SPLIT=0 keeps the plain kernel: host.h)
 constexpr long long HO_SPLIT_PAIRS = 2048;
-static bool ho_split_on() {
-  const char *e = getenv("GPSIG_HO_SPLIT");
-  return !(e && e[0] == '0');
-}
 
 template <int DP, int W, int ORD, int SEED, bool TILE = false>
 static int launch_ho(const SigArgs &a0, long long nblocks, hipStream_t s) {
@@ -411,56 +405,36 @@ int ho_lanes_per_pair(int l2, int order, int M) { return (M <= 8 && order <= 8 &
 template <int DP, int SEED, bool TILE = false>
 static int ho_dispatch(const SigArgs &a, long long nblocks, hipStream_t s) {
   const int W = ho_w(a.l2, a.order);
-  switch (a.order) {
-#define ORDCASE(o)                                                          \
-  case o:                                                                   \
-    if (W == 1) return launch_ho<DP, 1, o, SEED, TILE>(a, nblocks, s);      \
-    if constexpr (o <= 5) {                                                 \
-      if (W == 2) return launch_ho<DP, 2, o, SEED, TILE>(a, nblocks, s);    \
-    }                                                                       \
-    if constexpr (o <= 4) {                                                 \
-      if (W == 4) return launch_ho<DP, 4, o, SEED, TILE>(a, nblocks, s);    \
-    }                                                                       \
-    return GPSIG_EUNSUPPORTED;
-    ORDCASE(2) ORDCASE(3) ORDCASE(4) ORDCASE(5) ORDCASE(6) ORDCASE(7) ORDCASE(8)
-#undef ORDCASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<2, 3, 4, 5, 6, 7, 8>(a.order, [&](auto ord) {
+    constexpr int O = decltype(ord)::value;
+    if (W == 1) return launch_ho<DP, 1, O, SEED, TILE>(a, nblocks, s);
+    if constexpr (O <= 5) {
+      if (W == 2) return launch_ho<DP, 2, O, SEED, TILE>(a, nblocks, s);
+    }
+    if constexpr (O <= 4) {
+      if (W == 4) return launch_ho<DP, 4, O, SEED, TILE>(a, nblocks, s);
+    }
+    return (int)GPSIG_EUNSUPPORTED;
+  });
 }
 
 int sig_ho_launch(const SigArgs &a, int DP, int seed, long long nblocks, hipStream_t s) {
   if (seed != SEED_RBF_DIFF && seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
   if (a.M > 8 || a.order > 8 || a.order < 2) return GPSIG_EUNSUPPORTED;
-  switch (DP) {
-#define DCASE(v)                                                                          \
-  case v:                                                                                 \
-    return seed == SEED_RBF_DIFF ? ho_dispatch<v, SEED_RBF_DIFF>(a, nblocks, s)          \
-                                 : ho_dispatch<v, SEED_LIN_DIFF>(a, nblocks, s);
-    DCASE(4) DCASE(8) DCASE(16) DCASE(32)
-#undef DCASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<4, 8, 16, 32>(DP, [&](auto dp) {
+    constexpr int D = decltype(dp)::value;
+    return seed == SEED_RBF_DIFF ? ho_dispatch<D, SEED_RBF_DIFF>(a, nblocks, s)
+                                 : ho_dispatch<D, SEED_LIN_DIFF>(a, nblocks, s);
+  });
 }
 
 // ---- tile mode: the higher-order Gram past the fixed channel counts (linear base kernel, difference)
-void pde_tile_chunk(int n1, int l1, int n2, int l2, int pair_mode, int &rows, long long &cols);
-size_t pde_tile_scratch_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode);
-int increments_launch(const float *X, int n, int l, int d, float *dX, hipStream_t s);
-
-int mf_records(const float *X, int n, int l, int d, float *R, hipStream_t s);
-size_t mf_records_bytes(int n, int l, int d);
-bool mf_gram_applies(int d, int l2);
-int sig_fo_mf_cells(const float *FX, int n1, int l1, const float *FY, int n2, int l2, int d, int pair_mode,
-                    int row_begin, int row_end, float *dm, int dm_a0, int dm_b0, long long dm_as, long long dm_bs,
-                    long long dm_ld, hipStream_t s);
-
 bool ho_tiled(int d, int order) { return order > 1 && d > 32; }
-static size_t al256h(size_t b) { return (b + 255) & ~(size_t)255; }
 // the operands of a chunk's cells (linear: the increments; RBF: the matrix-core seed's records), then the tile
 static size_t ho_operand_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode) {
   const bool rect = pair_mode == GPSIG_PAIRS_RECT;
-  const size_t inc = al256h((size_t)n1 * (l1 - 1) * d * sizeof(float)) + (rect ? al256h((size_t)n2 * (l2 - 1) * d * sizeof(float)) : 0);
-  const size_t rec = al256h(mf_records_bytes(n1, l1, d)) + (rect ? al256h(mf_records_bytes(n2, l2, d)) : 0);
+  const size_t inc = align256((size_t)n1 * (l1 - 1) * d * sizeof(float)) + (rect ? align256((size_t)n2 * (l2 - 1) * d * sizeof(float)) : 0);
+  const size_t rec = align256(mf_records_bytes(n1, l1, d)) + (rect ? align256(mf_records_bytes(n2, l2, d)) : 0);
   return inc > rec ? inc : rec;
 }
 size_t ho_tile_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode) {
@@ -468,9 +442,8 @@ size_t ho_tile_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode) {
   int rows;
   long long cols;
   pde_tile_chunk(n1, l1, n2, l2, pair_mode, rows, cols);
-  return ho_operand_bytes(n1, l1, n2, l2, d, pair_mode) + al256h((size_t)rows * (l1 - 1) * cols * sizeof(float));
+  return ho_operand_bytes(n1, l1, n2, l2, d, pair_mode) + align256((size_t)rows * (l1 - 1) * cols * sizeof(float));
 }
-static inline long long ho_upper_prefix(long long r, long long ntb) { return r * ntb - 4 * r * (r - 1) / 2; }
 
 // Chunks of x-rows: the cell tile of the chunk -- linear: the increment Gram (one matrix-core GEMM dX_chunk dY^T,
 // batched per pair for DIAG); RBF: the difference-seed cells from the matrix-core wide seed (sig_fo_mf.h, cell
@@ -488,7 +461,7 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
   if (rbf ? !mf_gram_applies(d, l2) : seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
   char *w = static_cast<char *>(workspace);
   float *dX = reinterpret_cast<float *>(w), *dY = dX;
-  const size_t xb = rbf ? al256h(mf_records_bytes(n1, l1, d)) : al256h((size_t)n1 * IC * d * sizeof(float));
+  const size_t xb = rbf ? align256(mf_records_bytes(n1, l1, d)) : align256((size_t)n1 * IC * d * sizeof(float));
   if (pm == GPSIG_PAIRS_RECT) dY = reinterpret_cast<float *>(w + xb);
   float *T = reinterpret_cast<float *>(w + ho_operand_bytes(n1, l1, n2, l2, d, pm));
   int rc = rbf ? mf_records(X, n1, l1, d, dX, s) : increments_launch(X, n1, l1, d, dX, s);
@@ -507,13 +480,17 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
     SigArgs c = a;
     c.row_begin = c0;
     c.row_end = r1;
-    long long nblocks;
+    // one pair per wave: b-tiles are single sequences (G = 1)
+    PairTiles pt;
+    const int trc = pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, 1, &pt);
+    c.tiles_a0 = pt.tiles_a0;
+    c.ntb = pt.ntb;
+    c.tile_base = pt.tile_base;
     if (pm == GPSIG_PAIRS_DIAG) {
       c.tile_a0 = c0;
       c.tile_b0 = 0;
       c.tile_as = (long long)IC * IC;
       c.tile_ld = IC;
-      nblocks = (r1 - c0 + 3) / 4;
       if (rbf)
         rc = sig_fo_mf_cells(dX, n1, l1, dX, n1, l1, d, pm, c0, r1, T, c0, 0, (long long)IC * IC, 0, IC, s);
       else
@@ -527,15 +504,6 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
       c.tile_b0 = b0;
       c.tile_as = (long long)IC * tc;
       c.tile_ld = tc;
-      const int ta0 = r0 / 4, ta1 = (r1 + 3) / 4;
-      c.tiles_a0 = ta0;
-      c.ntb = n2;  // one pair per wave: b-tiles are single sequences
-      if (pm == GPSIG_PAIRS_RECT) {
-        nblocks = (long long)(ta1 - ta0) * n2;
-      } else {
-        c.tile_base = ho_upper_prefix(ta0, n2);
-        nblocks = ho_upper_prefix(ta1, n2) - c.tile_base;
-      }
       if (rbf)
         rc = sig_fo_mf_cells(dX, n1, l1, dY, n2, l2, d, pm, c0, r1, T, r0, b0, (long long)IC * tc, JC, tc, s);
       else
@@ -544,8 +512,8 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
                       pm == GPSIG_PAIRS_UPPER ? JC : 0, nullptr, 0);
     }
     if (rc) return rc;
-    if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
-    if ((rc = ho_dispatch<1, SEED_LIN_DIFF, true>(c, nblocks, s))) return rc;
+    if (trc) return trc;
+    if ((rc = ho_dispatch<1, SEED_LIN_DIFF, true>(c, pt.nblocks, s))) return rc;
   }
   return GPSIG_OK;
 }

@@ -1,6 +1,7 @@
 // gpsig_amd -- launches of the higher-order Gram VJP kernel (sig_ho_bwd.h): orders 2 (levels 2..8) and 3
 // (levels 3..5), the (order, levels) whose multiplier slab fits the LDS next to the cell buffer.  Orders
 // at or above the level count are the exact signature kernel: order min(order, M).
+#include "internal.h"
 #include "sig_ho_bwd_split.h"
 
 namespace gpsig {
@@ -43,6 +44,7 @@ size_t ho_bwd_slab_bytes(int l2, int order, int M) {
 
 // The LDS kernel runs one pair per workgroup: its own grid over the launch's rows [row_begin, row_end)
 static int ho_bwd_lds_launch(BwdArgs a, int o, int seed, hipStream_t s) {
+  // not pair_tiles: one pair per workgroup, so the tiles are single (a, b) pairs
   const int r0 = a.row_begin, r1 = a.row_end;
   long long nblocks;
   if (a.pair_mode == GPSIG_PAIRS_DIAG) {

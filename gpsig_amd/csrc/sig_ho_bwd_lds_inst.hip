@@ -1,8 +1,7 @@
 // gpsig_amd -- instantiations of the LDS-state higher-order Gram VJP (sig_ho_bwd_lds.h) for one effective
 // order (GPSIG_ORD): every level count whose multiplier slab fits the LDS, W = 4 (l2 <= 256) and 8 (l2 <= 512);
 // the split kernels (257 .. 509 points on 4 waves, 510 .. 1017 on 8 waves with a global slab).
-#include <stdlib.h>
-
+#include "internal.h"
 #include "sig_ho_bwd_split.h"
 
 #ifndef GPSIG_ORD
@@ -73,31 +72,22 @@ static int launch_split8(BwdArgs a, int seed, long long nblocks, hipStream_t s) 
   }
 }
 
-static bool split_on() {
-  const char *e = getenv("GPSIG_HO_SPLIT");
-  return !(e && e[0] == '0');
-}
-
 template <int ORD, int M>
 static int launch_lds_w(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
   // 510 .. 512 points at (order, levels) the 8-wave form does not hold keep the one-wave W = 8 kernel
   if (a.l2 > HO_SPLIT_NW * HO_SPLIT_CPB + 1 && ho_split8_ok(ORD, M)) return launch_split8<ORD, M>(a, seed, nblocks, s);
   if (a.l2 <= 256) return launch_lds<ORD, M, 4>(a, seed, nblocks, s);
-  if (split_on() && ho_bwd_split_fits(ORD, M, a.l2)) return launch_split<ORD, M>(a, seed, nblocks, s);
+  if (ho_split_on() && ho_bwd_split_fits(ORD, M, a.l2)) return launch_split<ORD, M>(a, seed, nblocks, s);
   return launch_lds<ORD, M, 8>(a, seed, nblocks, s);
 }
 
 template <>
 int sig_ho_bwd_lds_launch_o<GPSIG_ORD>(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
   constexpr int O = GPSIG_ORD;
-  switch (a.M) {
-#define GPSIG_CASE(m) \
-  case m:             \
-    if constexpr (m >= O) return launch_lds_w<O, m>(a, seed, nblocks, s); else return GPSIG_EUNSUPPORTED;
-    GPSIG_CASE(2) GPSIG_CASE(3) GPSIG_CASE(4) GPSIG_CASE(5) GPSIG_CASE(6) GPSIG_CASE(7) GPSIG_CASE(8)
-#undef GPSIG_CASE
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto lv) {
+    constexpr int M = decltype(lv)::value;
+    if constexpr (M >= O) return launch_lds_w<O, M>(a, seed, nblocks, s); else return (int)GPSIG_EUNSUPPORTED;
+  });
 }
 
 }  // namespace gpsig

@@ -9,7 +9,7 @@
 // components stream through the scalar cache while the sequence data is read time-major
 // (coalesced across lanes) from a feature buffer built per call.  Each lane streams its sequence in
 // time with O(num_levels^2) running sums; nothing (LT, T, N, L)-sized is materialised.
-#include "sig_common.h"
+#include "internal.h"
 
 namespace gpsig {
 
@@ -664,18 +664,7 @@ using namespace gpsig;
 // channel padding of the fixed instantiations; 0 = the runtime-channel (wide) instantiation
 static int dpad4(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 0; }
 
-namespace gpsig {
-int tvs_pk_launch(const float *Z, int lt, int t, int increments, int d, const float *Ft, int n, int l, int M,
-                  float *out, float *Zp, bool rbf, float *state, hipStream_t s);
-int tvs_wide_launch(const float *Z, int lt, int t, int increments, int d, const float *X, const float *Ft, int n,
-                    int l, int M, float *out, float *Zw, bool rbf, float *state, void *seedws, hipStream_t s);
-size_t tvs_pk_zp_bytes(int lt, int t, int d);
-size_t tvs_seed_bytes(int n, int l, int d, int lt, int t);
-}  // namespace gpsig
-
-static size_t tvs_ft_bytes(int n, int l, int d) {
-  return ((size_t)n * l * (2 * d + 3) * sizeof(float) + 255) & ~(size_t)255;
-}
+static size_t tvs_ft_bytes(int n, int l, int d) { return align256((size_t)n * l * (2 * d + 3) * sizeof(float)); }
 
 // time-major sequence features for other translation units (the tens-vs-seq VJP, sig_tvs_bwd.hip)
 namespace gpsig {
@@ -757,12 +746,6 @@ extern "C" int gpsig_tens_vs_seq_state(const float *Z, int lt, int t, int increm
                          tvs_seed_ws(workspace, n, l, d, lt, t), s);
   return rc == -1 ? GPSIG_EUNSUPPORTED : rc;
 }
-
-namespace gpsig {
-size_t tens_gram_mm_bytes(int lt, int t);
-int tens_gram_mm(const float *Z, int lt, int t, int incr, int d, int M, int rbf, float *out, void *workspace,
-                 size_t workspace_bytes, hipStream_t s);
-}  // namespace gpsig
 
 // Channel counts past 32 run the pair-tile kernel of the VJP (tens_vjp_mm.hip) and need a workspace.
 extern "C" size_t gpsig_tens_gram_workspace_bytes(int lt, int t, int d) {
@@ -949,7 +932,7 @@ static int rs_w(const RsArgs &a, int DP, hipStream_t s) {
 }
 
 extern "C" size_t gpsig_rescaled_workspace_bytes(int n, int num_levels) {
-  return ((size_t)n * num_levels * sizeof(float) + 255) & ~(size_t)255;
+  return align256((size_t)n * num_levels * sizeof(float));
 }
 
 extern "C" int gpsig_rescaled(const float *Z, int lt, int t, const float *X, int n, int l, int d, int num_levels,
@@ -961,28 +944,13 @@ extern "C" int gpsig_rescaled(const float *Z, int lt, int t, const float *X, int
   const int DP = d <= 8 ? dpad4(d) : 0;  // 0: runtime channel loop
   if (!workspace || workspace_bytes < gpsig_rescaled_workspace_bytes(n, num_levels)) return GPSIG_EWORKSPACE;
   RsArgs a{Z, X, lt, t, n, l, d, num_levels, embedding, out, static_cast<float *>(workspace)};
-  int rc;
-  switch (num_levels) {
-    case 1: rc = rs_w<1>(a, DP, s); break;
-    case 2: rc = rs_w<2>(a, DP, s); break;
-    case 3: rc = rs_w<3>(a, DP, s); break;
-    case 4: rc = rs_w<4>(a, DP, s); break;
-    case 5: rc = rs_w<5>(a, DP, s); break;
-    case 6: rc = rs_w<6>(a, DP, s); break;
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  const int rc = dispatch<1, 2, 3, 4, 5, 6>(num_levels, [&](auto m) { return rs_w<decltype(m)::value>(a, DP, s); });
   if (rc) return rc;
   const long long tot = (long long)num_levels * n * t;
   hipLaunchKernelGGL(rescaled_combine_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, out, a.kones,
                      num_levels, n, t);
   return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
-
-namespace gpsig {
-size_t tens_gram_vjp_mm_bytes(int lt, int t, int incr, int d, int rbf);
-int tens_gram_vjp_mm(const float *Z, int lt, int t, int incr, int d, int M, int rbf, const float *gout, float *gZ,
-                     void *workspace, size_t workspace_bytes, hipStream_t s);
-}  // namespace gpsig
 
 // Channel counts past 32 take the pair-tile + GEMM path (tens_vjp_mm.hip), which needs a workspace.
 extern "C" size_t gpsig_tens_gram_vjp_workspace_bytes(int lt, int t, int increments, int d, int num_levels,

@@ -1,17 +1,10 @@
 // gpsig_amd -- extern "C" entry of the tens-vs-seq VJP (include/gpsig_amd.h, gpsig_tens_vs_seq_vjp):
 // argument checks, time-major features, the kernel (sig_tvs_bwd.h) and the transpose of the
 // time-major sequence gradient into the caller's (n, l, d) buffer.
+#include "internal.h"
 #include "sig_tvs_bwd.h"
 
 namespace gpsig {
-size_t tvs_features_bytes(int n, int l, int d);
-int tvs_features_launch(const float *X, int n, int l, int d, float *Ft, hipStream_t s);
-template <int DP, bool INCR>
-int tvs_bwd_launch_dp(const TvsBwdArgs &a, int M, bool rbf, bool diff, hipStream_t s);
-size_t tvs_bwd_wide_workspace(int n, int l, int d, int lt, int t);
-int tvs_bwd_wide(const float *Z, int lt, int t, int incr, int d, const float *X, int n, int l, int M, bool rbf,
-                 bool diff, const float *gout, float *gZ, float *gX, const float *state, void *workspace,
-                 size_t workspace_bytes, hipStream_t s);
 
 // gX[seq][s][q] += gXt[(s * d + q) * n + seq]
 __global__ __launch_bounds__(256) void tvs_gx_add_kernel(const float *__restrict__ gXt, int n, int l, int d,
@@ -23,7 +16,6 @@ __global__ __launch_bounds__(256) void tvs_gx_add_kernel(const float *__restrict
   gX[idx] += gXt[(long long)r * n + seq];
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static int tvs_bwd_pad(int d) { return d <= 2 ? 2 : d <= 4 ? 4 : d <= 6 ? 6 : d <= 8 ? 8 : d <= 12 ? 12 : d <= 16 ? 16 : 0; }
 
 }  // namespace gpsig

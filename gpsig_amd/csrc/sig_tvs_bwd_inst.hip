@@ -1,5 +1,6 @@
 // One (channel padding, increments) instantiation set of the tens-vs-seq VJP kernel (sig_tvs_bwd.h),
 // compiled once per -DGPSIG_DP=.. -DGPSIG_INCR=.. so the sets build in parallel.
+#include "internal.h"
 #include "sig_tvs_bwd.h"
 #if !defined(GPSIG_DP) || !defined(GPSIG_INCR)
 #error "GPSIG_DP and GPSIG_INCR must be defined"
@@ -25,17 +26,8 @@ static int launch_tvs_bwd(const TvsBwdArgs &a, bool rbf, bool diff, hipStream_t 
 
 template <int DP, bool INCR>
 int tvs_bwd_launch_dp(const TvsBwdArgs &a, int M, bool rbf, bool diff, hipStream_t s) {
-  switch (M) {
-    case 1: return launch_tvs_bwd<DP, 1, INCR>(a, rbf, diff, s);
-    case 2: return launch_tvs_bwd<DP, 2, INCR>(a, rbf, diff, s);
-    case 3: return launch_tvs_bwd<DP, 3, INCR>(a, rbf, diff, s);
-    case 4: return launch_tvs_bwd<DP, 4, INCR>(a, rbf, diff, s);
-    case 5: return launch_tvs_bwd<DP, 5, INCR>(a, rbf, diff, s);
-    case 6: return launch_tvs_bwd<DP, 6, INCR>(a, rbf, diff, s);
-    case 7: return launch_tvs_bwd<DP, 7, INCR>(a, rbf, diff, s);
-    case 8: return launch_tvs_bwd<DP, 8, INCR>(a, rbf, diff, s);
-    default: return GPSIG_EUNSUPPORTED;
-  }
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(
+      M, [&](auto m) { return launch_tvs_bwd<DP, decltype(m)::value, INCR>(a, rbf, diff, s); });
 }
 
 template int tvs_bwd_launch_dp<GPSIG_DP, (GPSIG_INCR != 0)>(const TvsBwdArgs &, int, bool, bool, hipStream_t);

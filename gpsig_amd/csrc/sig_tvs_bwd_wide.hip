@@ -11,13 +11,10 @@
 //     [gX | rowsum] (s, n) += W0^T [Z0 | 1] + W1^T [Z1 | 1],    [gZ0 | colsum] += W0 [X | 1]
 // then gX -= rowsum x, gZ0 -= colsum z0 (RBF).  Linear: gX += W^T Zw (w = z, or z1 - z0), gZ = W X
 // (increments: gZ1 += W X, gZ0 -= W X).
-#include "sig_common.h"
+#include "internal.h"
 #include "gemm.h"
 
 namespace gpsig {
-
-size_t tvs_features_bytes(int n, int l, int d);
-int tvs_features_launch(const float *X, int n, int l, int d, float *Ft, hipStream_t s);
 
 struct TvsBwdWideArgs {
   const float *Zw;   // (T, [2,] d, LT) + (T, LT) |dz|^2/2: tvs_wide_prep_kernel layout
@@ -437,9 +434,6 @@ __global__ __launch_bounds__(256) void tvsw_gz_kernel(const float *__restrict__ 
   gZ[o] += sgn * (rbf ? __builtin_fmaf(-Gr[d], Z[o], Gr[q]) : Gr[q]);
 }
 
-static size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t tvs_tile_budget();  // sig_tvs_pk.hip (GPSIG_TVS_TILE_BYTES)
-
 struct TvswPlan {
   int nc;
   size_t ft, zw, za0, za1, xc, gxc, gz, w0, w1, part, sa, sdx, sd, sx;
@@ -451,23 +445,23 @@ static TvswPlan tvsw_plan(int n, int l, int d, int lt, int t, bool incr) {
   nc = nc < 64 ? 64 : (nc / 64) * 64;  // whole waves of sequences per chunk, or all of them in one
   if (nc > n) nc = n;
   p.nc = (int)nc;
-  p.ft = a256(tvs_features_bytes(n, l, d));
-  p.zw = a256((size_t)t * tvsw_zs(d, lt, true) * sizeof(float));
-  p.za0 = a256((size_t)lt * t * (d + 1) * sizeof(float));
+  p.ft = align256(tvs_features_bytes(n, l, d));
+  p.zw = align256((size_t)t * tvsw_zs(d, lt, true) * sizeof(float));
+  p.za0 = align256((size_t)lt * t * (d + 1) * sizeof(float));
   p.za1 = incr ? p.za0 : 0;
-  p.xc = a256((size_t)l * nc * (d + 1) * sizeof(float));
+  p.xc = align256((size_t)l * nc * (d + 1) * sizeof(float));
   p.gxc = p.xc;
-  p.gz = a256((size_t)lt * t * (d + 1) * sizeof(float) * (incr ? 2 : 1));
-  p.w0 = a256((size_t)lt * t * l * nc * sizeof(float));
+  p.gz = align256((size_t)lt * t * (d + 1) * sizeof(float) * (incr ? 2 : 1));
+  p.w0 = align256((size_t)lt * t * l * nc * sizeof(float));
   p.w1 = incr ? p.w0 : 0;
   const size_t pa = gemm_splitk_bytes((int)(l * nc), d + 1, lt * t);
   const size_t pb = gemm_splitk_bytes(lt * t, d + 1, (int)(l * nc));
   // gemm_f32 clamps the split of every chunk (the last, shorter one included) to this capacity
-  p.part = a256(pa > pb ? pa : pb);
-  p.sa = a256((size_t)lt * t * 2 * d * sizeof(float));
-  p.sdx = a256((size_t)(l - 1) * nc * d * sizeof(float));
-  p.sd = a256((size_t)lt * t * 2 * (l - 1) * nc * sizeof(float));
-  p.sx = a256((size_t)lt * t * l * nc * sizeof(float));
+  p.part = align256(pa > pb ? pa : pb);
+  p.sa = align256((size_t)lt * t * 2 * d * sizeof(float));
+  p.sdx = align256((size_t)(l - 1) * nc * d * sizeof(float));
+  p.sd = align256((size_t)lt * t * 2 * (l - 1) * nc * sizeof(float));
+  p.sx = align256((size_t)lt * t * l * nc * sizeof(float));
   return p;
 }
 static size_t tvsw_bytes(const TvswPlan &p) {
@@ -546,18 +540,9 @@ int tvs_bwd_wide(const float *Z, int lt, int t, int incr, int d, const float *X,
         return rc;
     }
     TvsBwdWideArgs a{Zw, Ft, t, n, l, d, lt, gout, state, n0, nc, W0, W1 ? W1 : W0, SD, SX, cd, cx};
-    switch (M) {
-      case 1: rc = launch_tvsw<1>(a, incr, rbf, diff, s); break;
-      case 2: rc = launch_tvsw<2>(a, incr, rbf, diff, s); break;
-      case 3: rc = launch_tvsw<3>(a, incr, rbf, diff, s); break;
-      case 4: rc = launch_tvsw<4>(a, incr, rbf, diff, s); break;
-      case 5: rc = launch_tvsw<5>(a, incr, rbf, diff, s); break;
-      case 6: rc = launch_tvsw<6>(a, incr, rbf, diff, s); break;
-      case 7: rc = launch_tvsw<7>(a, incr, rbf, diff, s); break;
-      case 8: rc = launch_tvsw<8>(a, incr, rbf, diff, s); break;
-      default: return GPSIG_EUNSUPPORTED;
-    }
-    if (rc) return rc;
+    if ((rc = dispatch<1, 2, 3, 4, 5, 6, 7, 8>(
+             M, [&](auto m) { return launch_tvsw<decltype(m)::value>(a, incr, rbf, diff, s); })))
+      return rc;
     const int R = l * nc;
     // sequence side: the chunk's point gradients, rows (s, j)
     if ((rc = gemm_f32(s, true, false, R, D1, (int)zr, 1.0f, W0, R, 0, Za0, D1, 0, 0.0f, Gxc, D1, 0, 1, 0, 0, part, pl.part)))

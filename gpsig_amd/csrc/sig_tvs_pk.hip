@@ -13,10 +13,8 @@
 // k (and Ep) are re-evaluated exactly every ANCHOR (32) cells.  Arguments past the polynomial range take
 // expm1 = e^x - 1 (a wave-uniform branch); with increments, |q| or |c| >= 2 (far-apart corners) takes
 // the plain corner difference of directly evaluated base-kernel values.
-#include <stdlib.h>
-
 #include "gemm.h"
-#include "sig_common.h"
+#include "internal.h"
 
 namespace gpsig {
 
@@ -352,8 +350,7 @@ struct TvsWideArgs {
 // seed-tile budget of one chunk of sequences (GPSIG_TVS_TILE_BYTES overrides it: the tests force several
 // chunks; read per call, so the workspace query and the launch agree)
 size_t tvs_tile_budget() {
-  const char *e = getenv("GPSIG_TVS_TILE_BYTES");
-  const long long v = e ? atoll(e) : 0;
+  const long long v = env_ll("GPSIG_TVS_TILE_BYTES", 0);
   return v > 0 ? (size_t)v : (size_t)1 << 30;
 }
 
@@ -369,9 +366,9 @@ inline TvsSeedPlan tvs_seed_plan(int n, int l, int d, int lt, int t) {
   nc = nc < 64 ? 64 : (nc / 64) * 64;  // whole waves of sequences per chunk ...
   if (nc > n) nc = n;                   // ... or every sequence in one chunk (fewer than 64 only then)
   p.nc = (int)nc;
-  p.a = (((size_t)t * lt * 2 * d * sizeof(float)) + 255) & ~(size_t)255;
-  p.dx = (((size_t)nc * (l - 1) * d * sizeof(float)) + 255) & ~(size_t)255;
-  p.s = (((size_t)nc * (l - 1) * t * lt * 2 * sizeof(float)) + 255) & ~(size_t)255;
+  p.a = align256((size_t)t * lt * 2 * d * sizeof(float));
+  p.dx = align256((size_t)nc * (l - 1) * d * sizeof(float));
+  p.s = align256((size_t)nc * (l - 1) * t * lt * 2 * sizeof(float));
   return p;
 }
 
@@ -701,15 +698,10 @@ static int launch_tvs_pk(const float *Z, int lt, int t, int d, const float *Ft, 
 template <int DP, bool INCR>
 static int tvs_pk_m(int M, const float *Z, int lt, int t, int d, const float *Ft, int n, int l, float *out, float *Zp,
                     bool rbf, float *state, hipStream_t s) {
-  switch (M) {
-    case 1: return launch_tvs_pk<DP, 1, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    case 2: return launch_tvs_pk<DP, 2, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    case 3: return launch_tvs_pk<DP, 3, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    case 4: return launch_tvs_pk<DP, 4, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    case 5: return launch_tvs_pk<DP, 5, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    case 6: return launch_tvs_pk<DP, 6, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
-    default: return -1;
-  }
+  if (M < 1 || M > 6) return -1;
+  return dispatch<1, 2, 3, 4, 5, 6>(M, [&](auto m) {
+    return launch_tvs_pk<DP, decltype(m)::value, INCR>(Z, lt, t, d, Ft, n, l, out, Zp, rbf, state, s);
+  });
 }
 
 // -1: not covered by the fast path (the caller runs the general kernel)
@@ -731,7 +723,7 @@ int tvs_pk_launch(const float *Z, int lt, int t, int increments, int d, const fl
 size_t tvs_pk_zp_bytes(int lt, int t, int d) {
   // the packed paths' (T, LT, ZS) buffer (d <= 8) or the wide kernels' (T, 2d + 1, LT) one
   const int DP = d <= 2 ? 2 : d <= 4 ? 4 : d <= 6 ? 6 : d <= 8 ? 8 : d;
-  return ((size_t)lt * t * ((2 * DP + 2)) * sizeof(float) + 255) & ~(size_t)255;
+  return align256((size_t)lt * t * ((2 * DP + 2)) * sizeof(float));
 }
 
 }  // namespace gpsig

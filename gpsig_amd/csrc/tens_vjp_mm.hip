@@ -18,7 +18,7 @@
 // channel-window kernel it replaces (sig_tens.hip, tens_gram_vjp_kernel<16, true>) recomputed the
 // component kernels once per 16-channel window of the gradient.
 #include "gemm.h"
-#include "sig_common.h"
+#include "internal.h"
 
 namespace gpsig {
 
@@ -250,8 +250,6 @@ __global__ __launch_bounds__(256) void tgv_levels_kernel(const float *__restrict
   }
 }
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct TgvPlan {
   size_t m, kv, P, G;
 };
@@ -260,9 +258,9 @@ TgvPlan tgv_plan(int lt, int t, int incr, int d, int rbf) {
   const long long T2 = (long long)t * t;
   const int H = (rbf && incr) ? 2 : 1;
   TgvPlan p;
-  p.m = al256((size_t)lt * T2 * sizeof(float));
-  p.kv = al256((size_t)lt * (rbf && incr ? 4 : 1) * T2 * sizeof(float));
-  p.P = al256((size_t)lt * H * t * (d + 1) * sizeof(float));
+  p.m = align256((size_t)lt * T2 * sizeof(float));
+  p.kv = align256((size_t)lt * (rbf && incr ? 4 : 1) * T2 * sizeof(float));
+  p.P = align256((size_t)lt * H * t * (d + 1) * sizeof(float));
   p.G = p.P;
   return p;
 }
@@ -274,7 +272,7 @@ size_t tens_gram_vjp_mm_bytes(int lt, int t, int incr, int d, int rbf) {
   return p.m + p.kv + p.P + p.G;
 }
 
-size_t tens_gram_mm_bytes(int lt, int t) { return al256((size_t)lt * t * t * sizeof(float)); }
+size_t tens_gram_mm_bytes(int lt, int t) { return align256((size_t)lt * t * t * sizeof(float)); }
 
 // The forward tensor Gram past 32 channels: the VJP's pair-tile kernel (component kernels over all channels
 // staged through LDS) and the level products

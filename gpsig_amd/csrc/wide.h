@@ -62,7 +62,6 @@ __host__ __device__ inline long long wide_rec_floats(int d, int l) { return (lon
 //   fp32 values as the fixed-channel feature records (sig_fo.hip features_kernel).
 __global__ __launch_bounds__(256) void wide_records_kernel(const float *__restrict__ X, int n, int l, int d,
                                                            float *__restrict__ R);
-int wide_records(const float *X, int n, int l, int d, float *R, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Seed tiles of the diagonal's self-pairs (RBF difference seed, order 1; sig_bwd_wide.hip): per pair a,
@@ -75,10 +74,7 @@ constexpr int DIAG_TILE_ANCHOR = 4;
 struct DiagTiles {
   long long rows, ld, pair;  // RP, NC, floats per pair
 };
-DiagTiles diag_tiles_of(int l, int W, int LP);
-bool diag_tiles_apply(int l, int d, int W, int LP, int seed, int order);
-int wide_diag_tiles(const float *FX, long long sx, int d, int lw, int a0, int npairs, DiagTiles dt, float *T,
-                    hipStream_t s);
+// (diag_tiles_of, diag_tiles_apply, wide_diag_tiles: internal.h)
 // pairs per tile chunk (DIAG_TILE_BYTES of tiles)
 constexpr size_t DIAG_TILE_BYTES = (size_t)512 << 20;
 inline int diag_tile_pairs(const DiagTiles &dt, int n) {

@@ -36,28 +36,25 @@ def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def workspace(device, nbytes: int) -> torch.Tensor:
-    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
+def _cached_buffer(device, nbytes: int, *tag) -> torch.Tensor:
+    """The cached uint8 buffer of (tag, device, current stream), grown to at least nbytes (1 MiB at least)."""
+    key = tag + (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
     with _ws_lock:
         buf = _ws.get(key)
         if buf is None or buf.numel() < nbytes:
             buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
             _ws[key] = buf
         return buf
+
+
+def workspace(device, nbytes: int) -> torch.Tensor:
+    return _cached_buffer(device, nbytes)
 
 
 def scratch(device, nbytes: int):
     """A second per-stream cached buffer for calls that take a workspace AND a scratch (the PDE adjoint's
     fronts plus the increment tiles); None when nothing is needed."""
-    if nbytes <= 0:
-        return None
-    key = ("scratch", torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
-    with _ws_lock:
-        buf = _ws.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-            _ws[key] = buf
-        return buf
+    return _cached_buffer(device, nbytes, "scratch") if nbytes > 0 else None
 
 
 def _sp(buf):
