@@ -209,15 +209,17 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 GPSIG_DEV f2 splat2(float v) { return (f2){v, v}; }
 GPSIG_DEV f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-GPSIG_DEV f2 em1_small2(f2 x) {
+// P5(x) of em1_small2(x) = x * P5(x), for callers that fuse the closing product into a sum themselves
+GPSIG_DEV f2 em1_small2_poly(f2 x) {
   f2 p = splat2(1.388882549e-03f);
   p = fma2(p, x, splat2(8.407682727e-03f));
   p = fma2(p, x, splat2(4.166870013e-02f));
   p = fma2(p, x, splat2(1.666597426e-01f));
   p = fma2(p, x, splat2(4.999998314e-01f));
   p = fma2(p, x, splat2(1.000000095e+00f));
-  return p * x;
+  return p;
 }
+GPSIG_DEV f2 em1_small2(f2 x) { return em1_small2_poly(x) * x; }
 
 // N independent em1 evaluations, Horner steps interleaved across the N chains (back-to-back
 // dependent v_pk_fma_f32 would otherwise be padded with s_nop).

@@ -361,12 +361,22 @@ struct RbfSeedPk {
   // and slow rows, straight from the record).
   struct Row {
     float dx[DP], g;
-    const float *fr;  // record of row i; x_{i+1} = fr[FS .. FS + DP)
+    // record of row i; x_{i+1} = fr[FS .. FS + DP).  Constant address space: the records are read through
+    // the scalar cache in every instantiation (the 10-lane groups took them through the vector path)
+    cfloat *fr;
     GPSIG_DEV void load(const float *__restrict__ fx, int i) {
-      fr = fx + (long long)i * FS;
+      fr = as_const(fx) + (long long)i * FS;
 #pragma unroll
       for (int k = 0; k < DP; ++k) dx[k] = fr[DP + k];
       g = fr[2 * DP + 1];
+    }
+    // member by member (a whole-struct copy in the row loop kept the record in memory: same symptom as at
+    // p0_dot)
+    GPSIG_DEV void set(const Row &o) {
+      fr = o.fr;
+#pragma unroll
+      for (int k = 0; k < DP; ++k) dx[k] = o.dx[k];
+      g = o.g;
     }
   };
 
@@ -375,6 +385,91 @@ struct RbfSeedPk {
 #pragma unroll
     for (int k = 0; k < DP; ++k) x1[k] = rd.fr[FS + k];
     exact(x1, Eqo, ko);
+  }
+
+  // p of column pair 0 for the row with record rd.  It reads no row state, so the hot loop takes it a row
+  // ahead (sig_fo.h), where its serial chain of packed FMAs has the level recursion to hide behind.
+  // It reads through the record's pointer (the same loads as Row::load's, merged with them).  Splats of
+  // members of a Row that is carried round a loop were turned (hipcc of ROCm 7.2) into two-float loads of the
+  // struct, which then is not promoted to registers.  Symptom in the row loop's assembly: ds_write / ds_read
+  // of the record and global_load instead of s_load for it.
+  GPSIG_DEV f2 p0_dot(const Row &rd) const {
+    f2 a = splat2(-rd.fr[2 * DP + 1]);
+#pragma unroll
+    for (int k = 0; k < DP; ++k) a = fma2(y[0][k], splat2(rd.fr[DP + k]), a);
+    return a;
+  }
+
+  // The seed of row i shared by row() and row_hot(): the dots c (every pair), p from pair 0's p0 by the
+  // column recurrence described at row(), the polynomials, and the product-form cells into dM from the
+  // current kc, Eq (neither is written).  Returns the lane's range-check value max |p|, |c|.
+  template <bool CLO>
+  GPSIG_DEV float cells(const Row &rd, f2 p0, f2 (&p)[W2], f2 (&c)[W2], f2 (&Ec)[W2], f2 (&Ep)[W2],
+                        f2 (&dM)[W2]) const {
+    // channel-major, so the pairs' dots (each a serial chain of packed FMAs) are written interleaved: a
+    // packed result read by the very next instruction costs a wait state
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2) c[w2] = dy[w2][0] * splat2(rd.dx[0]);
+#pragma unroll
+    for (int k = 1; k < DP; ++k)
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2) c[w2] = fma2(dy[w2][k], splat2(rd.dx[k]), c[w2]);
+    p[0] = p0;
+#pragma unroll
+    for (int w2 = 1; w2 < W2; ++w2) p[w2] = p[w2 - 1] + c[w2 - 1];
+    if constexpr (CLO)
+      em1_lo2_n<W2>(c, Ec);
+    else
+      em1_small2_n<W2>(c, Ec);
+    // Ep[1] = Ep[0] + t with Ep[0] = p P(p) is the FMA p P(p) + t, written out: left as a sum it is fused
+    // or not by where the branches of the row loop fall (the former two-row loop of W <= 4 fused it on odd
+    // rows only; the W >= 8 loops on every row)
+    const f2 Pp = em1_small2_poly(p[0]);
+    Ep[0] = Pp * p[0];
+    float mx = 0.0f;
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2) {
+      const f2 t = fma2(Ep[w2], Ec[w2], Ec[w2]);  // (1 + Ep) Ec
+      if (w2 + 1 < W2) Ep[w2 + 1] = w2 == 0 ? fma2(Pp, p[0], t) : Ep[w2] + t;
+      const f2 t2 = fma2(Eq[w2], t, t);
+      {
+        // the cell is a rounded product: never contracted into the level recursion's C_1 += dM
+#pragma clang fp contract(off)
+        dM[w2] = kc[w2] * fma2(Ep[w2], Eq[w2], t2);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        // CLO: every Ec is in the cubic's range a priori, and the pairs after the first take Ep by the exact
+        // chain Ep' = Ep + (1 + Ep) Ec, so only the first pair's p meets a polynomial
+        if constexpr (CLO) {
+          if (w2 == 0 || !GPSIG_P0CHECK) mx = __builtin_fmaxf(mx, __builtin_fabsf(p[w2][h]));
+        } else {
+          mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
+        }
+      }
+    }
+    return mx;
+  }
+
+  // Row i of the hot loop (sig_fo.h), p0 = p0_dot(rd): the cells into dM, then kc, Eq and kcR advanced in
+  // place by the row-to-row recurrences.  Returns true, with kc, Eq and kcR untouched, when a cell of the
+  // wave is outside the polynomial range: the caller then runs row() on the same record (the slow path),
+  // which recomputes the same seed.  No exact evaluation lives here, so the loop around it carries its
+  // state in place.
+  template <bool CLO>
+  GPSIG_DEV bool row_hot(const Row &rd, f2 p0, f2 (&dM)[W2]) {
+    f2 p[W2], c[W2], Ec[W2], Ep[W2];
+    const float mx = cells<CLO>(rd, p0, p, c, Ec, Ep, dM);
+    if (GPSIG_NAIVE && __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0) return true;
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2) {
+      // Eq + Ec is a rounded sum: Ec's final product x P(x) is not contracted into it
+#pragma clang fp contract(off)
+      kc[w2] = fma2(kc[w2], Ep[w2], kc[w2]);
+      Eq[w2] = fma2(Eq[w2], Ec[w2], Eq[w2] + Ec[w2]);
+    }
+    kcR = lane_next(kc[0][0]);
+    return false;
   }
 
   // Cells of row i into dM.  anch (wave-uniform): the next row's state is re-evaluated exactly
@@ -407,45 +502,8 @@ struct RbfSeedPk {
       row_pc(rd, anch, p, c, dM);
       return;
     }
-#pragma unroll
-    for (int w2 = 0; w2 < W2; ++w2) {
-      f2 cc = dy[w2][0] * splat2(rd.dx[0]);
-#pragma unroll
-      for (int k = 1; k < DP; ++k) cc = fma2(dy[w2][k], splat2(rd.dx[k]), cc);
-      c[w2] = cc;
-    }
-    {
-      f2 a = splat2(-rd.g);
-#pragma unroll
-      for (int k = 0; k < DP; ++k) a = fma2(y[0][k], splat2(rd.dx[k]), a);
-      p[0] = a;
-    }
-#pragma unroll
-    for (int w2 = 1; w2 < W2; ++w2) p[w2] = p[w2 - 1] + c[w2 - 1];
     f2 Ec[W2], Ep[W2];
-    if constexpr (CLO)
-      em1_lo2_n<W2>(c, Ec);
-    else
-      em1_small2_n<W2>(c, Ec);
-    Ep[0] = em1_small2(p[0]);
-    float mx = 0.0f;
-#pragma unroll
-    for (int w2 = 0; w2 < W2; ++w2) {
-      const f2 t = fma2(Ep[w2], Ec[w2], Ec[w2]);  // (1 + Ep) Ec
-      if (w2 + 1 < W2) Ep[w2 + 1] = Ep[w2] + t;
-      const f2 t2 = fma2(Eq[w2], t, t);
-      dM[w2] = kc[w2] * fma2(Ep[w2], Eq[w2], t2);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        // CLO: every Ec is in the cubic's range a priori, and the pairs after the first take Ep by the exact
-        // chain Ep' = Ep + (1 + Ep) Ec, so only the first pair's p meets a polynomial
-        if constexpr (CLO) {
-          if (w2 == 0 || !GPSIG_P0CHECK) mx = __builtin_fmaxf(mx, __builtin_fabsf(p[w2][h]));
-        } else {
-          mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
-        }
-      }
-    }
+    const float mx = cells<CLO>(rd, p0_dot(rd), p, c, Ec, Ep, dM);
     const bool slow = GPSIG_NAIVE && __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
     if (anch || slow) {
       f2 Eqn[W2], kn[W2];

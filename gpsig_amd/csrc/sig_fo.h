@@ -37,7 +37,9 @@ constexpr int WIDE_R = GPSIG_WIDE_R;
 // recursion, no output), 2 = consumer (cells streamed from p.dmbuf through the recursion and epilogue).
 // Waves per SIMD the register allocation must leave room for: 2 (256 VGPRs) where W = 8 columns per lane
 // only just fit at D = 7..8 (the allocator would otherwise take 260 and run one wave per SIMD, 1.6x
-// slower; at 256 it spills a few registers outside the row loop).
+// slower; at 256 it spills a few registers outside the row loop), and for the packed RBF seed at W = 8,
+// M <= 6 at every D: its row loop (runs of hot rows, below) takes 259 at D = 5, M = 5 left to itself, where
+// the former loop fitted 230.  Everything else is compiled as it was.
 // per-row record type of the row loop: the seed's own (wide, packed RBF) or the generic RowData
 template <bool WIDE, bool PK, class PS, int DP, int W>
 struct FoRec { using type = RowData<DP>; };
@@ -46,13 +48,16 @@ struct FoRec<true, PK, PS, DP, W> { using type = typename PS::Row; };
 template <class PS, int DP, int W>
 struct FoRec<false, true, PS, DP, W> { using type = typename RbfSeedPk<DP, W>::Row; };
 
-__host__ __device__ constexpr int fo_waves(int DP, int W, int M) { return ((W == 8 && DP > 6 && M <= 6) || W == 10) ? 2 : 1; }
+__host__ __device__ constexpr int fo_waves(int DP, int W, int M, int SEED) {
+  const bool pk8 = SEED == SEED_RBF_DIFF && W == 8 && DP >= 1 && M <= 6;
+  return ((W == 8 && DP > 6 && M <= 6) || W == 10 || pk8) ? 2 : 1;
+}
 
 template <int DP, int W, int LP, int M, int SEED, bool DIAGK, bool SAVE = false, bool MF = false, int SPLIT = 0>
 #ifdef GPSIG_FO_LB
 #define GPSIG_FO_BOUNDS __launch_bounds__(256, GPSIG_FO_LB)
 #else
-#define GPSIG_FO_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP, W, M))))
+#define GPSIG_FO_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP, W, M, SEED))))
 #endif
 __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
   // DP == 0: wide channel counts (runtime p.wd, channel-major records, wide.h)
@@ -163,39 +168,11 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
 #pragma unroll
       for (int w2 = 0; w2 < W2; ++w2) C[m][w2] = splat2(0.0f);
 
-    // One row: seed cells, then the level recursion.  S_m = exclusive prefix over (rows < i, cols < j)
-    // of R_m = exclusive scan over j of C_m; the M-1 scans are independent and interleave.
+    // One row: seed cells (do_row below, or the hot loop's row_hot), then the level recursion (levels).
+    // S_m = exclusive prefix over (rows < i, cols < j) of R_m = exclusive scan over j of C_m; the M-1 scans
+    // are independent and interleave.
     using Rec = typename FoRec<WIDE, PK, PSeed, DP, W>::type;
-    auto do_row = [&](auto clo_t, int i, const Rec &rd, bool anch, const f2 *pc = nullptr) {
-      f2 dM[W2];
-      if constexpr (SPLIT == 2) {
-        const f4 *src = reinterpret_cast<const f4 *>(dms + (long long)i * (LP * W));
-#pragma unroll
-        for (int w4 = 0; w4 < W / 4; ++w4) {
-          const f4 v = __builtin_nontemporal_load(src + w4);
-          dM[2 * w4] = (f2){v[0], v[1]};
-          dM[2 * w4 + 1] = (f2){v[2], v[3]};
-        }
-      } else if constexpr (WIDE) {
-        seed.template row<decltype(clo_t)::value>(rd, anch, dM);
-      } else if constexpr (PK) {
-        if (MF && pc) {
-          f2 pp[W2], cc[W2];
-#pragma unroll
-          for (int w2 = 0; w2 < W2; ++w2) {
-            pp[w2] = pc[w2];
-            cc[w2] = pc[W2 + w2];
-          }
-          seed.row_pc(rd, anch, pp, cc, dM);
-        } else {
-          seed.template row<decltype(clo_t)::value>(rd, anch, dM);
-        }
-      } else {
-        float d1[W];
-        seed.template row<true>(rd, d1);
-#pragma unroll
-        for (int w2 = 0; w2 < W2; ++w2) dM[w2] = (f2){d1[w2], d1[w2 + W2]};
-      }
+    auto levels = [&](int i, const f2 (&dM)[W2]) {
       if constexpr (SPLIT == 1) {
         f4 *dst = reinterpret_cast<f4 *>(dms + (long long)i * (LP * W));
 #pragma unroll
@@ -248,15 +225,44 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
 #pragma unroll
       for (int w2 = 0; w2 < W2; ++w2) C[0][w2] += dM[w2];
     };
+    auto do_row = [&](auto clo_t, int i, const Rec &rd, bool anch, const f2 *pc = nullptr) {
+      f2 dM[W2];
+      if constexpr (SPLIT == 2) {
+        const f4 *src = reinterpret_cast<const f4 *>(dms + (long long)i * (LP * W));
+#pragma unroll
+        for (int w4 = 0; w4 < W / 4; ++w4) {
+          const f4 v = __builtin_nontemporal_load(src + w4);
+          dM[2 * w4] = (f2){v[0], v[1]};
+          dM[2 * w4 + 1] = (f2){v[2], v[3]};
+        }
+      } else if constexpr (WIDE) {
+        seed.template row<decltype(clo_t)::value>(rd, anch, dM);
+      } else if constexpr (PK) {
+        if (MF && pc) {
+          f2 pp[W2], cc[W2];
+#pragma unroll
+          for (int w2 = 0; w2 < W2; ++w2) {
+            pp[w2] = pc[w2];
+            cc[w2] = pc[W2 + w2];
+          }
+          seed.row_pc(rd, anch, pp, cc, dM);
+        } else {
+          seed.template row<decltype(clo_t)::value>(rd, anch, dM);
+        }
+      } else {
+        float d1[W];
+        seed.template row<true>(rd, d1);
+#pragma unroll
+        for (int w2 = 0; w2 < W2; ++w2) dM[w2] = (f2){d1[w2], d1[w2 + W2]};
+      }
+      levels(i, dM);
+    };
     // Row loop.  For the packed RBF seed the row recurrences are re-anchored every ANCH rows (a
     // wave-uniform branch); the other seeds evaluate every row directly.  The saved-state launch of a
     // training step uses the same period, so it writes the inference launch's Gram bit for bit (the
     // VJP, which regenerates its cells from an exact row every 4 rows, inverts the saved sums with
     // cells that differ from these by the recurrences' rounding drift, ~1e-7 relative).
     constexpr int ANCH = PSeed::ANCHOR;
-#ifndef GPSIG_FO_UNROLL2
-#define GPSIG_FO_UNROLL2 (W <= 4)
-#endif
     int i = 0;
     if constexpr (PK && MF) {
       static_assert(ANCH % 4 == 0, "anchor period");
@@ -307,15 +313,52 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
           if constexpr (WIDE_R > 7) one(std::integral_constant<int, 7>{});
         }
       } else {
-      if constexpr (PK && GPSIG_FO_UNROLL2 && !MF) {
-        // row pairs: ANCHOR is even, so the first row of a pair never anchors (compile-time)
-        static_assert(ANCH % 2 == 0, "anchor period");
-        for (; i + 2 <= nrows; i += 2) {
-          Rec r0, r1;
-          r0.load(fx, i);
-          r1.load(fx, i + 1);
-          do_row(clo_t, i, r0, false);
-          do_row(clo_t, i + 1, r1, ((i + 1) % ANCH) == ANCH - 1);
+      if constexpr (PK && !MF && SPLIT != 2 && GPSIG_PCHAIN) {
+        // Runs of hot rows (RbfSeedPk::row_hot: no exact evaluation in the body, so kc, Eq and kcR are
+        // advanced in their registers), each ended by the row that needs the exact path: the anchor row, or
+        // a row with a cell outside the polynomial range, which leaves the run before any state is written
+        // and is evaluated again, whole, by row().  The record of row i + 1 (clamped to the last row) is
+        // loaded before row i's arithmetic, so its scalar-cache latency is not waited for, and that row's
+        // p0_dot closes row i, so the range check that opens a row finds it done.
+        // A slow row hands the record it had loaded ahead to the run after it.
+        //
+        // Three things here answer what hipcc of ROCm 7.2 made of the plain form, not the algorithm; what
+        // to look for in the assembly of the inner loop (one instantiation, -S) to see whether each is still
+        // needed:
+        //  - the slow row's cur.set(nxt) (and not a reload) is also a second reader of the record: with the
+        //    body as its only reader the s_load of the record moves into the body's block and is issued
+        //    beside its first use.  Symptom: s_waitcnt lgkmcnt(0) within ~10 instructions of the record's
+        //    s_load_dword(x4), instead of the loads standing in the block that opens the row.
+        //  - the sched_barrier closing the body keeps the run's prologue and the end of the body distinct.
+        //    Without it their common tail (the record loads and p0_dot) is merged into the loop header.
+        //    Symptom: s_load of the record, s_waitcnt lgkmcnt(0) and a chain of five v_pk_fma_f32 with
+        //    s_nop 0 between them at the top of the loop, ahead of the range check's v_cmp.
+        //  - p0_dot reads through the record's pointer, see there.
+        constexpr bool CLO = decltype(clo_t)::value;
+        Rec cur, nxt;  // records of rows i and (inside a run) i + 1
+        if (i < nrows) cur.load(fx, i);
+        while (i < nrows) {
+          const int stop = min(nrows, i - i % ANCH + ANCH - 1);  // the next anchor row
+          f2 p0 = seed.p0_dot(cur);
+          bool slow = false;
+          for (; i < stop; ++i) {
+            nxt.load(fx, min(i + 1, nrows - 1));
+            f2 dM[W2];
+            slow = seed.template row_hot<CLO>(cur, p0, dM);
+            if (slow) break;
+            levels(i, dM);
+            p0 = seed.p0_dot(nxt);
+            cur.set(nxt);
+            __builtin_amdgcn_sched_barrier(0);  // see above
+          }
+          if (i < nrows) {  // cur is row i's record on every way here
+            do_row(clo_t, i, cur, true);
+            ++i;
+            if (slow)
+              cur.set(nxt);
+            else if (i < nrows)
+              cur.load(fx, i);
+          }
         }
       }
       for (; i < nrows; ++i) {
