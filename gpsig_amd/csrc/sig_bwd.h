@@ -271,6 +271,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_W
   cfloat *fxc = as_const(fx);  // row records: scalar loads, independent of the atomics below
   const float *__restrict__ fy = p.FY + (long long)bl * l2 * FS;
   const int nrows = DIFF ? l1 - 1 : l1;
+  // Self pair (one sequence on both sides, RBF): the weight on (x_i, y_i) multiplies k (y_i - x_i) = 0 and is
+  // dropped in emit.  Kept, it enters A and B - A y below with k = 1 and leaves ~6e-8 |y_i| of rounding per row
+  // next to terms that carry a small k (jumps, far-apart points): 1.1e-5 of the gradient at L = 256, D = 8 with
+  // x 25 steps on every sequence (tests/test_vjp_regimes_gpu.py), 7e-7 without it.
+  const bool self = RBF && fx == fy;
+  const bool self_any = __builtin_amdgcn_ballot_w64(self) != 0;
 
   // ---- column blocks: block k holds the cells j0 .. j0 + CPB - 1 on the points j0 .. j0 + CPB (j0 = k CPB)
   const int nblk = (LP == 64) ? p.nblk : 1;
@@ -627,6 +633,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_W
       for (int w = 0; w < W; ++w) {
         const float v = RBF ? Kh[w] * kr[w] : Kh[w];
         wg[w] = ptv[w] ? v : 0.0f;
+      }
+      if (self_any) {
+        const int wd = self ? pi - j0 - gl * W : -1;  // this lane's column on the diagonal, if any
+#pragma unroll
+        for (int w = 0; w < W; ++w) wg[w] = w == wd ? 0.0f : wg[w];
       }
       float s[DP + 1];
 #pragma unroll

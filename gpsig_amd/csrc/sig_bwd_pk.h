@@ -170,6 +170,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWDPK
   const float *__restrict__ fy = p.FY + (long long)bl * l2 * FS;
   using SegF = std::conditional_t<SEG, SegFactors<SEG ? LP : 10>, char>;
   const SegF segf{};
+  // self pair (one sequence on both sides, RBF): the weight on (x_i, y_i) multiplies k (y_i - x_i) = 0 and is
+  // dropped in emit, as in sig_bwd_kernel (sig_bwd.h: kept, its rounding in B - A y outweighs small-k terms)
+  const bool self = RBF && fx == fy;
+  const bool self_any = __builtin_amdgcn_ballot_w64(self) != 0;
 
   // ---- column data: pair w2 of this lane holds columns j = gl W + w2 + h W2 (h = 0, 1); points past the
   // sequence clamp to its last one, columns without a cell get a zero increment (their product-form cells
@@ -546,6 +550,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWDPK
     f2 wg[W2];
 #pragma unroll
     for (int w2 = 0; w2 < W2; ++w2) wg[w2] = RBF ? Kh[w2] * kr[w2] : Kh[w2];
+    if (self_any) {
+      const int wd = self ? pi - gl * W : -1;  // this lane's column w2 + h W2 on the diagonal, if any
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) wg[w2][h] = w2 + h * W2 == wd ? 0.0f : wg[w2][h];
+    }
     f2 s[DP], st = wg[0];
 #pragma unroll
     for (int k = 0; k < DP; ++k) s[k] = wg[0] * y[0][k];
