@@ -5,7 +5,9 @@ Python host on PyTorch-ROCm tensors; the recursions run in hand-written gfx950 H
 """
 from . import kernels, kernels_pde, ops  # noqa: F401
 from ._lib import GpsigError, load  # noqa: F401
-from .kernels import (SignatureKernel, SignatureLinear, SignatureRBF, SignatureGauss)  # noqa: F401
+from .kernels import (SignatureKernel, SignatureLinear, SignatureRBF, SignatureGauss,  # noqa: F401
+                      SignatureMatern12, SignatureMatern32, SignatureMatern52, SignatureLaplace,
+                      SignatureExponential)
 from .kernels_pde import UntruncSignatureKernel  # noqa: F401
 
 __version__ = "0.1.0"

@@ -33,6 +33,9 @@ _ERRORS = {
 
 BASE_RBF = 0
 BASE_LINEAR = 1
+BASE_MATERN12 = 2  # forward only (gpsig_sig_gram / gpsig_sig_diag)
+BASE_MATERN32 = 3
+BASE_MATERN52 = 4
 BASE_SEED_MFMA = 0x100  # flag: RBF seed dots on the matrix cores (A/B arm, include/gpsig_amd.h)
 GRAM_SPLIT = 0x200  # flag: split producer/consumer diagnostic of the first-order Gram (include/gpsig_amd.h)
 PAIRS_RECT, PAIRS_UPPER, PAIRS_DIAG = 0, 1, 2

@@ -247,11 +247,21 @@ def _epilogue(Kr, sc, cfg):
     return K if cfg["return_levels"] else K.sum(0)
 
 
+def _no_vjp(cfg):
+    """Base kernels with a forward seed only (the Matern family): the forward saves no VJP state."""
+    return ops.forward_only(cfg["base"])
+
+
+def _raise_no_vjp(cfg):
+    raise NotImplementedError(f"the {cfg['base']} base kernel has no VJP kernel in this build (the Matern Gram VJP is "
+                              "not built): its signature kernels are forward only")
+
+
 def _folded(cfg, X2s, lengths, needs_grad):
     """Normalised K whose backward folds the normalisation's diagonal terms into the weights of the diagonal
     pairs (one VJP launch, see SigGram.backward): the forward keeps the raw levels (and, for K(X, X2), the raw
     diagonals).  Order 1: symmetric K(X); higher orders: under the higher-order VJP kernel, K(X) and K(X, X2)."""
-    if not (needs_grad and cfg["normalization"]):
+    if not (needs_grad and cfg["normalization"]) or _no_vjp(cfg):
         return False
     if cfg["order"] == 1 or cfg["num_levels"] == 1:
         return X2s is None
@@ -334,7 +344,7 @@ class SigGram(torch.autograd.Function):
             rs2 = rs1 if X2s is None else ops.sig_diag(X2s.detach(), M, jitter=cfg["jitter"], rsqrt=True, **kw)
         jit = cfg["jitter"] if (cfg["normalization"] and X2s is None) else 0.0
         state = None
-        if any(ctx.needs_input_grad[:3]) and cfg["order"] == 1 and cfg["difference"]:
+        if any(ctx.needs_input_grad[:3]) and cfg["order"] == 1 and cfg["difference"] and not _no_vjp(cfg):
             n2 = None if X2s is None else X2s.shape[0]
             numel = ops.sig_state_numel(Xs.shape[0], n2, Xs.shape[1] if X2s is None else X2s.shape[1], M)
             state = _saved_buffer(numel, Xs.device, GRAM_STATE_BYTES)
@@ -349,6 +359,8 @@ class SigGram(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         cfg = ctx.cfg
+        if _no_vjp(cfg):
+            _raise_no_vjp(cfg)
         if ctx.folded:
             # dLoss/dK_m(a, b) of the epilogue in fp64, the diagonal's own term (through 1/sqrt(K_m(a, a)))
             # included in the weight of the pair (a, a): ONE VJP launch over the upper triangle.  The diagonal
@@ -462,6 +474,8 @@ class SigDiag(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         cfg = ctx.cfg
+        if _no_vjp(cfg):
+            _raise_no_vjp(cfg)
         (Xs,) = ctx.saved_tensors
         if cfg["order"] != 1 and not _ho_vjp_kernel(cfg, Xs.shape[1]):
             _check_bwd(cfg, gram=True)

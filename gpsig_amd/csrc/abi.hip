@@ -46,7 +46,15 @@ static size_t feat_bytes(int n, int l, int d) {
 static int seed_of(int base_kind, int difference) {
   if (base_kind == GPSIG_BASE_RBF) return difference ? SEED_RBF_DIFF : SEED_RBF_POINT;
   if (base_kind == GPSIG_BASE_LINEAR) return difference ? SEED_LIN_DIFF : SEED_LIN_POINT;
+  if (base_kind >= GPSIG_BASE_MATERN12 && base_kind <= GPSIG_BASE_MATERN52) return difference ? SEED_RAD_DIFF : SEED_RAD_POINT;
   return -1;
+}
+
+// The radial profile k(r) = (1 + c1 s + c2 s^2) e^(-s), s = a r, of a Matern kind (kernels.py:1135-1173)
+static void radial_profile_of(int base_kind, SigArgs *a) {
+  a->rad_a = base_kind == GPSIG_BASE_MATERN52 ? 2.2360679774997897f : base_kind == GPSIG_BASE_MATERN32 ? 1.7320508075688772f : 1.0f;
+  a->rad_c1 = base_kind == GPSIG_BASE_MATERN12 ? 0.0f : 1.0f;
+  a->rad_c2 = base_kind == GPSIG_BASE_MATERN52 ? (float)(1.0 / 3.0) : 0.0f;
 }
 
 // the wide diagonal's seed tiles (wide.h DiagTiles, RBF difference seed): one chunk of pairs
@@ -156,6 +164,7 @@ static int sig_gram_impl(const float *X, int n1, int l1, const float *Y, int n2,
                                            state != nullptr, &pl);
   if (seed < 0 || (!planned && !tiled)) return GPSIG_EUNSUPPORTED;
   if (pl.wide && (mfma || split)) return GPSIG_EUNSUPPORTED;
+  if (state && seed_is_radial(seed)) return GPSIG_EUNSUPPORTED;  // forward only: no VJP reads a saved state
   if (row_end == row_begin) return GPSIG_OK;
 
   SigArgs a{};
@@ -173,6 +182,7 @@ static int sig_gram_impl(const float *X, int n1, int l1, const float *Y, int n2,
   a.out_rows = out_rows;
   a.out_ld = n2;
   a.out_lvl = pair_mode == GPSIG_PAIRS_DIAG ? (long long)n1 : (long long)out_rows * n2;
+  if (seed_is_radial(seed)) radial_profile_of(base_kind, &a);
   if (tiled) return sig_ho_tiled(a, X, Y, d, seed, workspace, workspace_bytes, s);
 
   const int DP = pl.DP;

@@ -252,6 +252,7 @@ extern "C" int gpsig_sig_gram_vjp_ho(const float *X, int n1, int l1, const float
 extern "C" size_t gpsig_sig_vjp_ho_workspace_bytes(int n1, int l1, int n2, int l2, int d, int num_levels, int order,
                                                    int base_kind) {
   if (n1 <= 0 || n2 <= 0 || l1 < 2 || l2 < 2 || d <= 0 || order < 1) return 0;
+  if (vjp_seed(base_kind, true) < 0) return 0;  // base kinds without a VJP (the Matern family)
   if (order == 1 || num_levels == 1) return gpsig_sig_vjp_workspace_bytes(n1, l1, n2, l2, d, num_levels, 1);
   const int seed = vjp_seed(base_kind, true);
   VjpPlan p;

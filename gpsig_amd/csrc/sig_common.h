@@ -2,6 +2,8 @@
 // the per-point feature layout, the pair-tile scheduler, the fused normalisation epilogue and the
 // per-row seed (base-kernel second difference).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace gpsig {
@@ -15,8 +17,14 @@ enum Seed : int {
   SEED_RBF_DIFF = 0,    // stable/naive hybrid second difference of exp(-|x-y|^2/2)
   SEED_LIN_DIFF = 1,    // <dx_i, dy_j>
   SEED_RBF_POINT = 2,   // exp(-|x_i-y_j|^2/2)  (difference=False)
-  SEED_LIN_POINT = 3    // <x_i, y_j>           (difference=False)
+  SEED_LIN_POINT = 3,   // <x_i, y_j>           (difference=False)
+  // radial profile k(r) = (1 + c1 s + c2 s^2) e^(-s), s = a r, r = |x - y| (the Matern family; a, c1, c2 at run
+  // time in SigArgs): RadialSeed below, RadialSeedWide in wide.h
+  SEED_RAD_DIFF = 4,    // second difference of the k grid, x-difference first (stable), then over the columns
+  SEED_RAD_POINT = 5    // k(x_i, y_j)          (difference=False)
 };
+__host__ __device__ constexpr bool seed_is_diff(int s) { return s == SEED_RBF_DIFF || s == SEED_LIN_DIFF || s == SEED_RAD_DIFF; }
+__host__ __device__ constexpr bool seed_is_radial(int s) { return s == SEED_RAD_DIFF || s == SEED_RAD_POINT; }
 
 struct SigArgs {
   const float *FX, *FY;  // feature records (n1,l1,FS), (n2,l2,FS)
@@ -58,6 +66,8 @@ struct SigArgs {
   const float *dtile;
   int dt_a0;
   long long dt_pair, dt_rows, dt_ld;
+  // radial seeds: k(r) = (1 + rad_c1 s + rad_c2 s^2) e^(-s), s = rad_a r (wave-uniform)
+  float rad_a, rad_c1, rad_c2;
 };
 
 // Saved forward state of a first-order pair (gpsig_sig_gram_state): column sums of levels 1..M-1
@@ -67,14 +77,14 @@ __host__ __device__ inline long long state_slot(int a, int b, int n2, bool upper
   return upper ? (long long)a * n2 - (long long)a * (a - 1) / 2 + (b - a) : (long long)a * n2 + b;
 }
 
-// Wave-uniform record of row i: x_{i+1} (RBF DIFF) or x_i (POINT seeds), dx_i, |dx_i|^2/2.
+// Wave-uniform record of row i: x_{i+1} (RBF and radial DIFF) or x_i (POINT seeds), dx_i, |dx_i|^2/2.
 template <int DP>
 struct RowData {
   float x[DP], dx[DP], hdx, g;
   GPSIG_DEV void load(const float *__restrict__ fx, int i, int seed) {
     constexpr int FS = feat_stride(DP);
     const float *__restrict__ fr = fx + (long long)i * FS;
-    const float *__restrict__ fp = (seed == SEED_RBF_DIFF) ? fr + FS : fr;
+    const float *__restrict__ fp = (seed == SEED_RBF_DIFF || seed == SEED_RAD_DIFF) ? fr + FS : fr;
 #pragma unroll
     for (int k = 0; k < DP; ++k) {
       x[k] = fp[k];
@@ -229,6 +239,155 @@ struct RowSeed {
     }
   }
 };
+
+// ---------------------------------------------------------------------------------------------
+// Radial seeds (the Matern family, gpsig/kernels.py:1124-1173): k = P(s) e^(-s), P(s) = 1 + c1 s + c2 s^2,
+// s = a |x - y|; (a, c1, c2) = (1, 0, 0), (sqrt 3, 1, 0), (sqrt 5, 1, 1/3) are run-time values, so one
+// instantiation serves every smoothness.  Same interface as RowSeed.
+//
+// RAD_POINT: the k grid, one sqrt and one exp2 per cell.
+//
+// RAD_DIFF: dM = k11 - k10 - k01 + k00.  The plain fp32 corner difference loses up to 1.4e-5 of a level on random
+// walks, so the difference over the rows is taken first, in a form without cancellation, and the column
+// difference of that after it:
+//     delta = s1 - s0 = a <dx_i, 2 (x_i - y_j) + dx_i> / (r1 + r0)       (the dot, not d2_1 - d2_0)
+//     u(i, j) = k(x_{i+1}, y_j) - k(x_i, y_j) = e^(-s0) [ P(s1) expm1(-delta) + delta (c1 + c2 (s1 + s0)) ]
+//     dM(i, j) = u(i, j + 1) - u(i, j)
+// (P(s1) - P(s0) = delta (c1 + c2 (s1 + s0)) exactly.)  For c1 = 1 (the smooth profiles) the -delta of expm1 and
+// the +delta c1 cancel down to O(delta s) near r = 0, so the bracket is evaluated with that part taken out by hand,
+// expm1(x) = x + x^2 E2(x):
+//     u = e^(-s0) delta [ P(s1) delta E2(-delta) + (c1 - 1) + c2 (s1 + s0) - s1 (c1 + c2 s1) ]
+// r1 + r0 = 0 (repeated points, the diagonal of a self pair) has a zero numerator: delta = 0 and the cell is
+// exactly 0, where the reference clamps r^2 at 1e-40.
+// Outside the expm1 polynomial's range (|delta| >= EM1_TAU: k changes by 40 % or more over the step) u is the plain
+// difference P(s1) e^(-s1) - P(s0) e^(-s0), which loses nothing there and cannot overflow.  s and e^(-s) of row
+// i + 1 become row i's; each row evaluates |x_{i+1} - y_j|^2 directly, so nothing drifts.  The lane's last column
+// takes u of the next lane's first column.  Columns past the sequence repeat its last point, so their u are
+// equal and their cells exact zeros; the halo column of a column block is masked.
+
+// E2(x) = (expm1(x) - x) / x^2 on |x| < EM1_TAU: Taylor to x^6, 4.3e-8 relative truncation at the ends
+GPSIG_DEV float em2_small(float x) {
+  float p = 2.480158730e-05f;
+  p = __builtin_fmaf(p, x, 1.984126984e-04f);
+  p = __builtin_fmaf(p, x, 1.388888889e-03f);
+  p = __builtin_fmaf(p, x, 8.333333333e-03f);
+  p = __builtin_fmaf(p, x, 4.166666667e-02f);
+  p = __builtin_fmaf(p, x, 1.666666667e-01f);
+  return __builtin_fmaf(p, x, 0.5f);
+}
+// u = k(s1) - k(s0) of a radial profile (a, c1, c2 folded into the arguments): s0, e0 = e^(-s0), s1, e1 = e^(-s1),
+// num = <dx, 2 (x_{i+1} - y) - dx> = r1^2 - r0^2, a2 = a^2, c1m1 = c1 - 1
+GPSIG_DEV float radial_step(float s0, float e0, float s1, float e1, float num, float a2, float c1, float c1m1,
+                            float c2) {
+  const float den = s1 + s0;
+  const float delta = den > 0.0f ? a2 * num * __builtin_amdgcn_rcpf(den) : 0.0f;
+  const float q1 = __builtin_fmaf(c2, s1, c1), q0 = __builtin_fmaf(c2, s0, c1);
+  const float P1 = __builtin_fmaf(s1, q1, 1.0f), P0 = __builtin_fmaf(s0, q0, 1.0f);
+  const float g = __builtin_fmaf(-s1, q1, __builtin_fmaf(c2, den, c1m1));
+  const float stable = e0 * delta * __builtin_fmaf(P1 * delta, em2_small(-delta), g);
+  const float plain = __builtin_fmaf(P1, e1, -P0 * e0);
+  return __builtin_fabsf(delta) < EM1_TAU ? stable : plain;
+}
+
+// k of a radial profile at squared distance d2, fp64 (the closed form of level 1)
+GPSIG_DEV double radial_profile64(double d2, float a, float c1, float c2) {
+  const double s = (double)a * sqrt(d2);
+  return (1.0 + s * ((double)c1 + (double)c2 * s)) * exp(-s);
+}
+
+template <int DP, int W, int SEED>
+struct RadialSeed {
+  static_assert(seed_is_radial(SEED), "radial seeds");
+  static constexpr int FS = feat_stride(DP);
+  static constexpr bool DIFF = SEED == SEED_RAD_DIFF;
+  static constexpr int ANCHOR = 1 << 30;  // no row recurrence
+  static constexpr float L2E = 1.4426950408889634f;
+  float y[W][DP];
+  bool valid_last;  // DIFF: column W-1 of this lane is a real cell
+  bool valid[W];    // POINT
+  float ra, rc1, rc2;
+  float s0[W], e0[W];  // DIFF row state: s = a |x_i - y_j|, e^(-s)
+
+  GPSIG_DEV void set_profile(float a, float c1, float c2) {
+    ra = a;
+    rc1 = c1;
+    rc2 = c2;
+  }
+  // s = a |x - y_w|
+  GPSIG_DEV float dist(const float (&x)[DP], int w) const {
+    float d2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+      const float t = x[k] - y[w][k];
+      d2 = __builtin_fmaf(t, t, d2);
+    }
+    return ra * __builtin_amdgcn_sqrtf(d2);
+  }
+  GPSIG_DEV float profile(float s) const { return __builtin_fmaf(s, __builtin_fmaf(rc2, s, rc1), 1.0f); }
+
+  // set_profile first
+  GPSIG_DEV void init(const float *__restrict__ fx, const float *__restrict__ fy, int gl, int l2) {
+    const int ncols = DIFF ? l2 - 1 : l2;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const int j = gl * W + w;
+      valid[w] = j < ncols;
+      const int jj = j < l2 ? j : l2 - 1;
+      const float *f = fy + (long long)jj * FS;
+#pragma unroll
+      for (int k = 0; k < DP; ++k) y[w][k] = f[k];
+    }
+    valid_last = valid[W - 1];
+    if constexpr (DIFF) {
+      float x0[DP];
+#pragma unroll
+      for (int k = 0; k < DP; ++k) x0[k] = fx[k];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        s0[w] = dist(x0, w);
+        e0[w] = __builtin_amdgcn_exp2f(-s0[w] * L2E);
+      }
+    }
+  }
+
+  // Cells of row i.  rd = record of row i (x_{i+1} for DIFF, x_i for POINT).
+  template <bool ANCH>
+  GPSIG_DEV void row(const RowData<DP> &rd, float (&dM)[W]) {
+    if constexpr (DIFF) {
+      float u[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        float d2 = 0.0f, num = 0.0f;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) {
+          const float t = rd.x[k] - y[w][k];  // x_{i+1} - y_j
+          d2 = __builtin_fmaf(t, t, d2);
+          num = __builtin_fmaf(rd.dx[k], __builtin_fmaf(2.0f, t, -rd.dx[k]), num);
+        }
+        const float s1 = ra * __builtin_amdgcn_sqrtf(d2);
+        const float e1 = __builtin_amdgcn_exp2f(-s1 * L2E);
+        u[w] = radial_step(s0[w], e0[w], s1, e1, num, ra * ra, rc1, rc1 - 1.0f, rc2);
+        s0[w] = s1;
+        e0[w] = e1;
+      }
+      const float uR = lane_next(u[0]);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const float u1 = (w + 1 < W) ? u[w + 1] : uR;
+        dM[w] = (w + 1 < W || valid_last) ? u1 - u[w] : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const float s = dist(rd.x, w);
+        dM[w] = valid[w] ? profile(s) * __builtin_amdgcn_exp2f(-s * L2E) : 0.0f;
+      }
+    }
+  }
+};
+// the generic per-row seed of a seed kind
+template <int DP, int W, int SEED>
+using GenSeed = std::conditional_t<seed_is_radial(SEED), RadialSeed<DP, W, SEED>, RowSeed<DP, W, SEED>>;
 
 // ---------------------------------------------------------------------------------------------
 // RBF DIFF seed on column pairs (first-order kernel; W even).  Same cells as RowSeed<.., RBF_DIFF>,
@@ -624,11 +783,23 @@ struct RbfSeedPk {
 // once per pair in fp64.  The fp32 row sums of dM cancel down to K_1 and lose ~1e-7 of sum|dM|,
 // which is the whole error budget when K_1 is small against the cells (K_1 feeds only level 1).
 template <int DP, int SEED>
-GPSIG_DEV float level1_closed(const float *__restrict__ fx, const float *__restrict__ fy, int l1, int l2) {
+GPSIG_DEV float level1_closed(const float *__restrict__ fx, const float *__restrict__ fy, int l1, int l2,
+                               float ra = 0.0f, float rc1 = 0.0f, float rc2 = 0.0f) {
   constexpr int FS = feat_stride(DP);
   const float *x0 = fx, *xl = fx + (long long)(l1 - 1) * FS;
   const float *y0 = fy, *yl = fy + (long long)(l2 - 1) * FS;
-  if constexpr (SEED == SEED_RBF_DIFF) {
+  if constexpr (SEED == SEED_RAD_DIFF) {  // the radial profile (ra, rc1, rc2) at the four corners
+    auto k = [&](const float *a, const float *b) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        const double d = (double)a[c] - (double)b[c];
+        s = __builtin_fma(d, d, s);
+      }
+      return radial_profile64(s, ra, rc1, rc2);
+    };
+    return (float)((k(xl, yl) - k(xl, y0)) - (k(x0, yl) - k(x0, y0)));
+  } else if constexpr (SEED == SEED_RBF_DIFF) {
     auto k = [](const float *a, const float *b) {
       double s = 0.0;
 #pragma unroll

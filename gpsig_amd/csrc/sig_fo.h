@@ -50,7 +50,8 @@ struct FoRec<false, true, PS, DP, W> { using type = typename RbfSeedPk<DP, W>::R
 
 __host__ __device__ constexpr int fo_waves(int DP, int W, int M, int SEED) {
   const bool pk8 = SEED == SEED_RBF_DIFF && W == 8 && DP >= 1 && M <= 6;
-  return ((W == 8 && DP > 6 && M <= 6) || W == 10 || pk8) ? 2 : 1;
+  // (the radial seeds keep their row state beside the column points: the whole register file, no spills)
+  return ((W == 8 && DP > 6 && M <= 6 && !seed_is_radial(SEED)) || W == 10 || pk8) ? 2 : 1;
 }
 
 template <int DP, int W, int LP, int M, int SEED, bool DIAGK, bool SAVE = false, bool MF = false, int SPLIT = 0>
@@ -62,7 +63,7 @@ template <int DP, int W, int LP, int M, int SEED, bool DIAGK, bool SAVE = false,
 __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
   // DP == 0: wide channel counts (runtime p.wd, channel-major records, wide.h)
   constexpr bool WIDE = DP == 0;
-  constexpr bool DIFF = SEED == SEED_RBF_DIFF || SEED == SEED_LIN_DIFF;
+  constexpr bool DIFF = seed_is_diff(SEED);
   constexpr int FS = feat_stride(DP);
   constexpr int G = 64 / LP;
   // SEG: lane groups not aligned to DPP rows (LP = 10: G = 6 pairs per wave, lanes 60..63 idle)
@@ -115,7 +116,7 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
 
   constexpr bool PK = (SEED == SEED_RBF_DIFF) && !WIDE;
   using PSeed = std::conditional_t<WIDE, WideSeed<W, WIDE_R, SEED>,
-                                   std::conditional_t<PK, RbfSeedPk<DP, W>, RowSeed<DP, W, SEED>>>;
+                                   std::conditional_t<PK, RbfSeedPk<DP, W>, GenSeed<DP, W, SEED>>>;
   constexpr int W2 = W / 2;
   constexpr int ML = M > 1 ? M - 1 : 1;
   const int nrows = DIFF ? p.l1 - 1 : p.l1;
@@ -142,6 +143,7 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
     // points of this block: the DIFF seeds see the halo point, the point seeds do not
     const int npts = nblk == 1 ? p.l2 : min(p.l2 - j0, DIFF ? CPB + 1 : CPB);
     PSeed seed;
+    if constexpr (seed_is_radial(SEED)) seed.set_profile(p.rad_a, p.rad_c1, p.rad_c2);
     if constexpr (WIDE)
       seed.init(p.wd, p.lw1, p.lw2, fx, fy + j0, gl, npts);
     else
@@ -425,9 +427,9 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
   if (gl == 0 && pair_ok) {
     if constexpr (DIFF) {
       if constexpr (WIDE)
-        K[1] = level1_closed_wide<SEED>(fx, fy, p.wd, p.lw1, p.lw2, p.l1, p.l2);
+        K[1] = level1_closed_wide<SEED>(fx, fy, p.wd, p.lw1, p.lw2, p.l1, p.l2, p.rad_a, p.rad_c1, p.rad_c2);
       else
-        K[1] = level1_closed<DP, SEED>(fx, fy, p.l1, p.l2);
+        K[1] = level1_closed<DP, SEED>(fx, fy, p.l1, p.l2, p.rad_a, p.rad_c1, p.rad_c2);
     }
     store_pair<M>(p, a, b, K);
     if constexpr (SAVE) {  // raw levels K_1..K_M after the column sums
@@ -497,13 +499,13 @@ constexpr int FO_MAX_LEVELS = 8;
 template <int DP, int W, int LP, int M, int SEED, bool MF = false>
 int launch_fo(const SigArgs &a, long long nblocks, hipStream_t s) {
   if (nblocks <= 0) return GPSIG_OK;
-  constexpr bool DIFF = SEED == SEED_RBF_DIFF || SEED == SEED_LIN_DIFF;
+  constexpr bool DIFF = seed_is_diff(SEED);
   const size_t lds = LP == 64 ? fo_carry_bytes(a.l1, DIFF, M, a.nblk) : 0;
   if (lds > FO_MAX_CARRY_BYTES) return GPSIG_EUNSUPPORTED;
   if (a.pair_mode == GPSIG_PAIRS_DIAG) {
     hipLaunchKernelGGL((sig_fo_kernel<DP, W, LP, M, SEED, true, false, MF>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
   } else if (a.state) {
-    if constexpr (DIFF && !MF)
+    if constexpr (DIFF && !MF && !seed_is_radial(SEED))  // (no VJP, so no saved state, for the radial seeds)
       hipLaunchKernelGGL((sig_fo_kernel<DP, W, LP, M, SEED, false, true>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
     else
       return GPSIG_EUNSUPPORTED;

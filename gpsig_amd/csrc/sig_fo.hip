@@ -60,7 +60,7 @@ int sig_fo_launch(const SigArgs &a0, int DP, int seed, long long nblocks, hipStr
   const Geo g = DP == 0 ? fo_geometry_wide(a0.l2, seed) : fo_geometry(a0.l2, DP, a0.M, a0.mfma != 0, a0.dmbuf ? -1 : seed);
   if (g.W == 0) return GPSIG_EUNSUPPORTED;
   SigArgs a = a0;
-  a.nblk = fo_blocks(a0.l2, seed == SEED_RBF_DIFF || seed == SEED_LIN_DIFF, g);
+  a.nblk = fo_blocks(a0.l2, seed_is_diff(seed), g);
   return dispatch<0, 1, 2, 3, 4, 5, 6, 8>(DP, [&](auto dp) {
     return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto m) {
       return sig_fo_launch_dpm<decltype(dp)::value, decltype(m)::value>(a, seed, nblocks, s);

@@ -14,6 +14,8 @@ int sig_fo_launch_dpm(const SigArgs &a, int seed, long long nblocks, hipStream_t
     case SEED_LIN_DIFF: return fo_geo<DP, M, SEED_LIN_DIFF>(a, nblocks, s);
     case SEED_RBF_POINT: return fo_geo<DP, M, SEED_RBF_POINT>(a, nblocks, s);
     case SEED_LIN_POINT: return fo_geo<DP, M, SEED_LIN_POINT>(a, nblocks, s);
+    case SEED_RAD_DIFF: return fo_geo<DP, M, SEED_RAD_DIFF>(a, nblocks, s);
+    case SEED_RAD_POINT: return fo_geo<DP, M, SEED_RAD_POINT>(a, nblocks, s);
     default: return GPSIG_EUNSUPPORTED;
   }
 }

@@ -74,7 +74,7 @@ GPSIG_DEV void excl_scan_cols(const float (&v)[W], float (&out)[W], float *cr, i
 // blockIdx.x & 3), so the launches share the host's pair counts (x 4).
 template <int DP, int W, int ORD, int MMAX, int SEED, bool TILE = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void sig_ho_kernel(SigArgs p) {
-  using Seed = RowSeed<DP, W, SEED>;
+  using Seed = GenSeed<DP, W, SEED>;
   using Lay = HoLayout<ORD, MMAX>;
   constexpr int FS = feat_stride(DP);
   static_assert(!TILE || SEED == SEED_LIN_DIFF, "tile cells: linear difference seed");
@@ -132,6 +132,7 @@ __global__ __launch_bounds__(256) void sig_ho_kernel(SigArgs p) {
   const bool idle = SPLIT && blk >= nblk;
   const int j0 = idle ? 0 : blk * CPB;
   Seed seed;
+  if constexpr (seed_is_radial(SEED)) seed.set_profile(p.rad_a, p.rad_c1, p.rad_c2);
   if constexpr (!TILE) seed.init(fx, fy + (long long)j0 * FS, lane, nblk == 1 ? p.l2 : min(p.l2 - j0, CPB + 1));
   // TILE: this lane's cell columns of the block (the halo column of a block is not a cell of it)
   bool tcol[W];
@@ -359,7 +360,8 @@ __global__ __launch_bounds__(256) void sig_ho_kernel(SigArgs p) {
                       : (float)s[0];
   }
   if (lane == 0) {
-    if constexpr (!TILE) K[1] = level1_closed<DP, SEED>(fx, fy, p.l1, p.l2);  // ho seeds are the DIFF seeds
+    if constexpr (!TILE)  // ho seeds are the DIFF seeds
+      K[1] = level1_closed<DP, SEED>(fx, fy, p.l1, p.l2, p.rad_a, p.rad_c1, p.rad_c2);
     store_pair<MMAX>(p, a, b, K);
   }
 }
@@ -419,10 +421,11 @@ static int ho_dispatch(const SigArgs &a, long long nblocks, hipStream_t s) {
 }
 
 int sig_ho_launch(const SigArgs &a, int DP, int seed, long long nblocks, hipStream_t s) {
-  if (seed != SEED_RBF_DIFF && seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
+  if (!seed_is_diff(seed)) return GPSIG_EUNSUPPORTED;
   if (a.M > 8 || a.order > 8 || a.order < 2) return GPSIG_EUNSUPPORTED;
   return dispatch<4, 8, 16, 32>(DP, [&](auto dp) {
     constexpr int D = decltype(dp)::value;
+    if (seed == SEED_RAD_DIFF) return ho_dispatch<D, SEED_RAD_DIFF>(a, nblocks, s);
     return seed == SEED_RBF_DIFF ? ho_dispatch<D, SEED_RBF_DIFF>(a, nblocks, s)
                                  : ho_dispatch<D, SEED_LIN_DIFF>(a, nblocks, s);
   });

@@ -956,6 +956,7 @@ extern "C" int gpsig_rescaled(const float *Z, int lt, int t, const float *X, int
 extern "C" size_t gpsig_tens_gram_vjp_workspace_bytes(int lt, int t, int increments, int d, int num_levels,
                                                       int base_kind) {
   if (lt <= 0 || t <= 0 || d <= 0 || num_levels < 1 || dpad4(d) != 0) return 0;
+  if (base_kind != GPSIG_BASE_RBF && base_kind != GPSIG_BASE_LINEAR) return 0;  // no VJP for the other kinds
   return gpsig::tens_gram_vjp_mm_bytes(lt, t, increments ? 1 : 0, d, base_kind == GPSIG_BASE_RBF ? 1 : 0);
 }
 

@@ -428,18 +428,169 @@ struct WideSeedGen {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// The radial seeds (sig_common.h RadialSeed: same cells, same forms), wide channels.  One channel loop per
+// chunk of R rows gives |x - y_j|^2 of the chunk's points (POINT: rows i; DIFF: rows i + 1) and, for DIFF, the
+// numerator <dx_i, 2 (x_{i+1} - y_j) - dx_i> of the d^2 step; the profile follows per row.  DIFF row state
+// (s, e^(-s) of the current row) as in RadialSeed.
 template <int W, int R, int SEED>
-using WideSeed = std::conditional_t<SEED == SEED_RBF_DIFF, RbfSeedWide<W, R>, WideSeedGen<W, R, SEED>>;
+struct RadialSeedWide {
+  static_assert(seed_is_radial(SEED), "radial seeds");
+  static constexpr int W2 = W / 2;
+  static constexpr int ANCHOR = 1 << 30;
+  static constexpr bool DIFF = SEED == SEED_RAD_DIFF;
+  static constexpr float L2E = 1.4426950408889634f;
+  int d, lw, lwx;
+  cfloat *fx;
+  const float *fyc;
+  bool msk[W2][2];  // the lane's columns that are cells of the grid
+  float ra, rc1, rc2;
+  f2 s0[W2], e0[W2];          // DIFF row state
+  f2 cc[R][W2], nn[DIFF ? R : 1][W2];  // the chunk's d^2 and (DIFF) numerators
+  bool clo = false;
+
+  struct Row {
+    int i;
+    f2 c[W2], n[DIFF ? W2 : 1];
+  };
+
+  GPSIG_DEV void set_profile(float a, float c1, float c2) {
+    ra = a;
+    rc1 = c1;
+    rc2 = c2;
+  }
+  GPSIG_DEV void lcols(const float *base, int k, float (&v)[W]) const { ld_cols<W>(base + (long long)k * lw, v); }
+
+  // set_profile first
+  GPSIG_DEV void init(int d_, int lwx_, int lw_, const float *__restrict__ fxr, const float *__restrict__ fyblk, int gl,
+                      int npts) {
+    d = d_;
+    lw = lw_;
+    lwx = lwx_;
+    fx = as_const(fxr);
+    fyc = fyblk + gl * W;
+    const int ncols = DIFF ? npts - 1 : npts;
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) msk[w2][h] = gl * W + w2 + h * W2 < ncols;
+    if constexpr (DIFF) {  // s, e^(-s) of row 0
+      f2 s[W2];
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2) s[w2] = splat2(0.0f);
+      for (int k = 0; k < d; ++k) {
+        const float xv = fx[(long long)k * lwx];
+        float yv[W];
+        lcols(fyc, k, yv);
+#pragma unroll
+        for (int w2 = 0; w2 < W2; ++w2) {
+          const f2 df = splat2(xv) - (f2){yv[w2], yv[w2 + W2]};
+          s[w2] = fma2(df, df, s[w2]);
+        }
+      }
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          s0[w2][h] = ra * __builtin_amdgcn_sqrtf(s[w2][h]);
+          e0[w2][h] = __builtin_amdgcn_exp2f(-s0[w2][h] * L2E);
+        }
+    }
+  }
+  GPSIG_DEV void bound_c(int) {}
+
+  // rows i0 .. i0+R-1 (rows past the sequence read its padding: the last point, zero increments)
+  GPSIG_DEV void chunk(int i0) {
+    cfloat *xr0 = fx + i0 + (DIFF ? 1 : 0);
+    cfloat *dxr = fx + (long long)d * lwx + i0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2) {
+        cc[r][w2] = splat2(0.0f);
+        if constexpr (DIFF) nn[r][w2] = splat2(0.0f);
+      }
+    for (int k = 0; k < d; ++k) {
+      float xr[R], dr[DIFF ? R : 1];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        xr[r] = xr0[(long long)k * lwx + r];
+        if constexpr (DIFF) dr[r] = dxr[(long long)k * lwx + r];
+      }
+      float yv[W];
+      lcols(fyc, k, yv);
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int w2 = 0; w2 < W2; ++w2) {
+          const f2 df = splat2(xr[r]) - (f2){yv[w2], yv[w2 + W2]};
+          cc[r][w2] = fma2(df, df, cc[r][w2]);
+          if constexpr (DIFF) nn[r][w2] = fma2(splat2(dr[r]), fma2(splat2(2.0f), df, splat2(-dr[r])), nn[r][w2]);
+        }
+    }
+  }
+
+  template <int RR>
+  GPSIG_DEV Row row_of(int i) const {
+    Row rd;
+    rd.i = i;
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2) {
+      rd.c[w2] = cc[RR][w2];
+      if constexpr (DIFF) rd.n[w2] = nn[RR][w2];
+    }
+    return rd;
+  }
+
+  template <bool CLO = false>
+  GPSIG_DEV void row(const Row &rd, bool, f2 (&dM)[W2]) {
+    if constexpr (DIFF) {
+      f2 u[W2];
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float s1 = ra * __builtin_amdgcn_sqrtf(rd.c[w2][h]);
+          const float e1 = __builtin_amdgcn_exp2f(-s1 * L2E);
+          u[w2][h] = radial_step(s0[w2][h], e0[w2][h], s1, e1, rd.n[w2][h], ra * ra, rc1, rc1 - 1.0f, rc2);
+          s0[w2][h] = s1;
+          e0[w2][h] = e1;
+        }
+      // column w of the lane is (w % W2, w / W2); its right neighbour column w + 1, the next lane's column 0
+      const float uR = lane_next(u[0][0]);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const int w2 = w % W2, h = w / W2;
+        const float u1 = (w + 1 < W) ? u[(w + 1) % W2][(w + 1) / W2] : uR;
+        dM[w2][h] = msk[w2][h] ? u1 - u[w2][h] : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float s = ra * __builtin_amdgcn_sqrtf(rd.c[w2][h]);
+          const float k = __builtin_fmaf(s, __builtin_fmaf(rc2, s, rc1), 1.0f) * __builtin_amdgcn_exp2f(-s * L2E);
+          dM[w2][h] = msk[w2][h] ? k : 0.0f;
+        }
+    }
+  }
+};
+
+template <int W, int R, int SEED>
+using WideSeed = std::conditional_t<SEED == SEED_RBF_DIFF, RbfSeedWide<W, R>,
+                                    std::conditional_t<seed_is_radial(SEED), RadialSeedWide<W, R, SEED>,
+                                                       WideSeedGen<W, R, SEED>>>;
 
 // Level 1 in closed form (level1_closed, sig_common.h) on the wide records.
 template <int SEED>
 GPSIG_DEV float level1_closed_wide(const float *__restrict__ fx, const float *__restrict__ fy, int d, int lw1,
-                                   int lw2, int l1, int l2) {
+                                   int lw2, int l1, int l2, float ra = 0.0f, float rc1 = 0.0f, float rc2 = 0.0f) {
   double s00 = 0.0, s0l = 0.0, sl0 = 0.0, sll = 0.0, lin = 0.0;
   for (int k = 0; k < d; ++k) {
     const double x0 = fx[(long long)k * lw1], xl = fx[(long long)k * lw1 + l1 - 1];
     const double y0 = fy[(long long)k * lw2], yl = fy[(long long)k * lw2 + l2 - 1];
-    if constexpr (SEED == SEED_RBF_DIFF) {
+    if constexpr (SEED == SEED_RBF_DIFF || SEED == SEED_RAD_DIFF) {
       s00 = __builtin_fma(x0 - y0, x0 - y0, s00);
       s0l = __builtin_fma(x0 - yl, x0 - yl, s0l);
       sl0 = __builtin_fma(xl - y0, xl - y0, sl0);
@@ -448,7 +599,10 @@ GPSIG_DEV float level1_closed_wide(const float *__restrict__ fx, const float *__
       lin = __builtin_fma(xl - x0, yl - y0, lin);
     }
   }
-  if constexpr (SEED == SEED_RBF_DIFF)
+  if constexpr (SEED == SEED_RAD_DIFF)
+    return (float)((radial_profile64(sll, ra, rc1, rc2) - radial_profile64(sl0, ra, rc1, rc2)) -
+                   (radial_profile64(s0l, ra, rc1, rc2) - radial_profile64(s00, ra, rc1, rc2)));
+  else if constexpr (SEED == SEED_RBF_DIFF)
     return (float)((exp(-0.5 * sll) - exp(-0.5 * sl0)) - (exp(-0.5 * s0l) - exp(-0.5 * s00)));
   else
     return (float)lin;

@@ -11,7 +11,10 @@ The low-rank mode (``low_rank=True``: Nystrom features + randomized Hadamard pro
 gpsig/low_rank_calculations.py) runs through gpsig_amd/low_rank_calculations.py (torch GEMMs /
 eigh on the device; the fused gfx950 Gram kernels are exact and are not used there).  Not carried
 over ("Out of scope"): GPflow Parameter transforms/priors (parameters are plain
-tensors here), and base kernels without a gfx950 seed (Cosine, Poly, Mix, Spectral, Matern*).
+tensors here), and base kernels without a gfx950 seed (Cosine, Poly, Mix, Spectral).  The Matern
+kernels (SignatureMatern12 / Laplace / Exponential, SignatureMatern32, SignatureMatern52) have a forward
+seed: K, K_norms, Kdiag, K_seq_n_seq_covs and the low-rank mode work; their gradients and the
+inducing-tensor kernels (K_tens*) raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -45,7 +48,7 @@ def _as_tensor(X, device=None):
 class SignatureKernel:
     """Reference gpsig/kernels.py:16-940 (non-low-rank paths)."""
 
-    base = None  # set by subclasses: "rbf" | "linear"
+    base = None  # set by subclasses: "rbf" | "linear" | "matern12" | "matern32" | "matern52"
 
     def __init__(self, input_dim, num_features, num_levels, active_dims=None, variances=1, lengthscales=1, order=1,
                  normalization=True, difference=True, num_lags=None, low_rank=False, num_components=50,
@@ -189,10 +192,21 @@ class SignatureKernel:
     def _base_kern(self, X, X2=None):
         """Base kernel matrix between point sets (kernels.py:946-957, 979-986, 1042-1044)."""
         X2 = X if X2 is None else X2
+        if self.base == "linear":
+            return X @ X2.T
         if self.base == "rbf":
             sq = (X ** 2).sum(-1)[:, None] + (X2 ** 2).sum(-1)[None, :] - 2.0 * X @ X2.T
             return torch.exp(-sq / 2.0)
-        return X @ X2.T
+        # kernels.py:946-961: the squared distances in the reference's order of operations, clamped at 1e-40
+        sq = -2.0 * (X @ X2.T) + (X ** 2).sum(-1)[:, None] + (X2 ** 2).sum(-1)[None, :]
+        r = torch.sqrt(torch.clamp(sq, min=1e-40))
+        if self.base == "matern12":  # kernels.py:1135-1138
+            return torch.exp(-r)
+        if self.base == "matern32":  # kernels.py:1154-1157
+            return (1.0 + np.sqrt(3.0) * r) * torch.exp(-np.sqrt(3.0) * r)
+        if self.base == "matern52":  # kernels.py:1171-1173
+            return (1.0 + np.sqrt(5.0) * r + 5.0 / 3.0 * r * r) * torch.exp(-np.sqrt(5.0) * r)
+        raise NotImplementedError(f"base kernel {self.base!r}")
 
     def _lr_seeds(self, device):
         return torch.randint(0, 2 ** 31 - 1, (max(self.num_levels - 1, 1), 2), device="cpu")
@@ -306,8 +320,15 @@ class SignatureKernel:
         return (Kd if return_levels else Kd.sum(0)).to(dt)
 
     # ------------------------------------------------------------------ inducing tensors (kernels.py:544-704)
+    def _need_tensor_seed(self, what):
+        if ops.forward_only(self.base):
+            raise NotImplementedError(f"{type(self).__name__}.{what}: the inducing-tensor kernels have no "
+                                      f"{self.base} seed in this build (RBF and linear only); inducing sequences "
+                                      "(K, K_seq_n_seq_covs) and low_rank=True work")
+
     def _K_tens(self, Z, increments=False):
         """Raw per-level (num_levels+1, T, T) (kernels.py:264-284); differentiable in Z."""
+        self._need_tensor_seed("K_tens")
         cfg = self._cfg()
         cfg["increments"] = bool(increments)
         return _ag.TensGram.apply(Z, cfg)
@@ -318,6 +339,7 @@ class SignatureKernel:
 
     def _K_tens_vs_seq(self, Z, X, increments=False):
         """Raw per-level (num_levels+1, T, N) (kernels.py:314-341); differentiable in Z and X."""
+        self._need_tensor_seed("K_tens_vs_seq")
         cfg = self._cfg()
         cfg["increments"] = bool(increments)
         return _ag.TensVsSeq.apply(Z, X, cfg)
@@ -596,7 +618,8 @@ SignatureGauss = SignatureRBF
 class _Unsupported(SignatureKernel):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(f"{type(self).__name__}: this base kernel has no gfx950 seed in this build "
-                                  "(supported: SignatureRBF/SignatureGauss, SignatureLinear); see DESIGN.md")
+                                  "(supported: SignatureRBF/SignatureGauss, SignatureLinear, SignatureMatern12/"
+                                  "Laplace/Exponential, SignatureMatern32, SignatureMatern52); see DESIGN.md")
 
 
 class SignatureCosine(_Unsupported):
@@ -615,16 +638,19 @@ class SignatureSpectral(_Unsupported):
     """kernels.py:1074-1122 (not built)."""
 
 
-class SignatureMatern12(_Unsupported):
-    """kernels.py:1124-1138 (not built)."""
+class SignatureMatern12(SignatureKernel):
+    """kernels.py:1124-1138: exp(-r) state-space embedding (forward only: no gradients, no K_tens*)."""
+    base = "matern12"
 
 
-class SignatureMatern32(_Unsupported):
-    """kernels.py:1144-1157 (not built)."""
+class SignatureMatern32(SignatureKernel):
+    """kernels.py:1144-1157: (1 + sqrt(3) r) exp(-sqrt(3) r) (forward only)."""
+    base = "matern32"
 
 
-class SignatureMatern52(_Unsupported):
-    """kernels.py:1161-1173 (not built)."""
+class SignatureMatern52(SignatureKernel):
+    """kernels.py:1161-1173: (1 + sqrt(5) r + 5/3 r^2) exp(-sqrt(5) r) (forward only)."""
+    base = "matern52"
 
 
 SignatureLaplace = SignatureMatern12

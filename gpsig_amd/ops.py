@@ -15,7 +15,11 @@ from . import _lib as L
 _ws_lock = threading.Lock()
 _ws: dict = {}
 
-BASES = {"rbf": L.BASE_RBF, "gauss": L.BASE_RBF, "linear": L.BASE_LINEAR, "lin": L.BASE_LINEAR}
+BASES = {"rbf": L.BASE_RBF, "gauss": L.BASE_RBF, "linear": L.BASE_LINEAR, "lin": L.BASE_LINEAR,
+         "matern12": L.BASE_MATERN12, "laplace": L.BASE_MATERN12, "exponential": L.BASE_MATERN12,
+         "matern32": L.BASE_MATERN32, "matern52": L.BASE_MATERN52}
+# the Matern family: forward Gram / diagonal only (no VJP, no inducing-tensor kernels)
+FORWARD_ONLY = (L.BASE_MATERN12, L.BASE_MATERN32, L.BASE_MATERN52)
 
 
 def _require_cuda(*ts):
@@ -75,7 +79,13 @@ def base_kind(base) -> int:
     try:
         return BASES[base.lower()]
     except KeyError:
-        raise L.GpsigError(f"base kernel {base!r} has no gfx950 kernel (supported: rbf, linear)") from None
+        raise L.GpsigError(f"base kernel {base!r} has no gfx950 kernel (supported: rbf, linear, matern12, "
+                           "matern32, matern52)") from None
+
+
+def forward_only(base) -> bool:
+    """The base kernel has a forward seed only (the Matern family): no VJP, no inducing-tensor kernels."""
+    return (base_kind(base) & 0xFF) in FORWARD_ONLY
 
 
 # ----------------------------------------------------------------------------- truncated kernels

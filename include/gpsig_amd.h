@@ -41,6 +41,12 @@ enum gpsig_status {
 enum gpsig_base_kind {
   GPSIG_BASE_RBF = 0,    /* SignatureRBF._rbf      kernels.py:1042 : exp(-|x-y|^2/2)  */
   GPSIG_BASE_LINEAR = 1, /* SignatureLinear._lin   kernels.py:979  : <x, y>           */
+  /* The Matern family k(r) = (1 + c1 s + c2 s^2) exp(-s), s = a r, r = |x - y| (kernels.py:1124-1173):
+   * forward only (gpsig_sig_gram, gpsig_sig_diag: order 1 at any channel count, orders 2-8 up to 32
+   * channels); every other entry point returns GPSIG_EUNSUPPORTED for them, and so do the two flags below. */
+  GPSIG_BASE_MATERN12 = 2, /* SignatureMatern12 (Laplace, Exponential): exp(-r)                        */
+  GPSIG_BASE_MATERN32 = 3, /* SignatureMatern32: (1 + sqrt(3) r) exp(-sqrt(3) r)                       */
+  GPSIG_BASE_MATERN52 = 4, /* SignatureMatern52: (1 + sqrt(5) r + 5/3 r^2) exp(-sqrt(5) r)             */
   /* Flag OR-ed into base_kind of gpsig_sig_gram / gpsig_sig_diag (RBF, order 1, difference 1, no saved
    * state): evaluate the seed's increment inner products <y_j, dx_i>, <dy_j, dx_i> (the reference's
    * seed GEMM, kernels.py:946-957 + 1042-1044) on the matrix cores (v_mfma_f32_4x4x1_16b_f32) instead of
