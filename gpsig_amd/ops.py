@@ -518,6 +518,8 @@ def signature_vjp(X: torch.Tensor, depth: int, gout: torch.Tensor, gX: torch.Ten
         raise ValueError("gout must be (n, channels)")
     if gX is None:
         gX = torch.zeros((n, l, d), dtype=torch.float32, device=X.device)
+    if n == 0:
+        return gX
     ws = workspace(X.device, lib.gpsig_signature_workspace_bytes(n, d, depth, 1))
     L.check(lib.gpsig_signature_vjp_ex(X.data_ptr(), n, l, d, depth, gout.data_ptr(), gX.data_ptr(), ws.data_ptr(),
                                        ws.numel(), _stream(X.device)), "gpsig_signature_vjp")
@@ -654,11 +656,17 @@ EMBEDDINGS = {"linear": 0, "rbf": 1}
 def rescaled(Z: torch.Tensor, X: torch.Tensor, num_levels: int, embedding: str = "linear") -> torch.Tensor:
     """VOSF <S(x),(I - Lambda_t) S(x)> per level: Z (LT,T,D), X (N,L,D) -> (M+1, N, T)."""
     _require_cuda(Z, X)
+    lt, t, d = Z.shape
+    n, l, dx = X.shape
+    if dx != d:
+        raise ValueError("Z and X must have the same channel count")
+    if lt != num_levels * (num_levels + 1) // 2:
+        raise ValueError(f"Z must have num_levels*(num_levels+1)/2 = {num_levels * (num_levels + 1) // 2} components")
     lib = L.load()
     Z, X = _f32(Z), _f32(X)
-    lt, t, d = Z.shape
-    n, l, _ = X.shape
     out = torch.empty((num_levels + 1, n, t), dtype=torch.float32, device=X.device)
+    if n == 0:
+        return out
     ws = workspace(X.device, lib.gpsig_rescaled_workspace_bytes(n, num_levels))
     rc = lib.gpsig_rescaled(Z.data_ptr(), lt, t, X.data_ptr(), n, l, d, num_levels, EMBEDDINGS[embedding],
                             out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(X.device))
