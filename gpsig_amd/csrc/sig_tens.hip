@@ -867,23 +867,36 @@ __global__ __launch_bounds__(64) void tens_gram_vjp_kernel(TgBwdArgs a) {
           for (int q = 0; q < DP; ++q) g0[c][q] = __builtin_fmaf(w, zv(k, t2, 0, q), g0[c][q]);
         }
       } else if (a.rbf) {
-        // dM/dA1 = k(A1,B1)(B1 - A1) - k(A1,B0)(B0 - A1),  dM/dA0 = k(A0,B0)(B0 - A0) - k(A0,B1)(B1 - A0)
-        float e11 = 0.f, e10 = 0.f, e00 = 0.f, e01 = 0.f;
+        // dM/dA1 = k(A1,B1)(B1 - A1) - k(A1,B0)(B0 - A1),  dM/dA0 = k(A0,B0)(B0 - A0) - k(A0,B1)(B1 - A0),
+        // regrouped on dB = B1 - B0 so that a short increment does not cancel (the two products above agree
+        // to |dB| of their size):
+        //   dM/dA1 =  (k11 - k10)(B0 - A1) + k11 dB,   k11 - k10 = k10 expm1(<A1 - B0, dB> - |dB|^2/2)
+        //   dM/dA0 = -(k01 - k00)(B0 - A0) - k01 dB,   k01 - k00 = k00 expm1(<A0 - B0, dB> - |dB|^2/2)
+        float e11 = 0.f, e10 = 0.f, e00 = 0.f, e01 = 0.f, q1 = 0.f, q0 = 0.f, hdb = 0.f;
 
         for (int q = 0; q < nq; ++q) {
           const float a0 = zv(k, t1, 0, q), a1 = zv(k, t1, 1, q), b0 = zv(k, t2, 0, q), b1 = zv(k, t2, 1, q);
+          const float db = b1 - b0;
           e11 = __builtin_fmaf(a1 - b1, a1 - b1, e11);
           e10 = __builtin_fmaf(a1 - b0, a1 - b0, e10);
           e00 = __builtin_fmaf(a0 - b0, a0 - b0, e00);
           e01 = __builtin_fmaf(a0 - b1, a0 - b1, e01);
+          q1 = __builtin_fmaf(a1 - b0, db, q1);
+          q0 = __builtin_fmaf(a0 - b0, db, q0);
+          hdb = __builtin_fmaf(db, db, hdb);
         }
-        const float k11 = w * fast_exp(-0.5f * e11), k10 = w * fast_exp(-0.5f * e10);
-        const float k00 = w * fast_exp(-0.5f * e00), k01 = w * fast_exp(-0.5f * e01);
+        q1 -= 0.5f * hdb;
+        q0 -= 0.5f * hdb;
+        const float k11 = fast_exp(-0.5f * e11), k10 = fast_exp(-0.5f * e10);
+        const float k00 = fast_exp(-0.5f * e00), k01 = fast_exp(-0.5f * e01);
+        const float d1 = w * (__builtin_fabsf(q1) < EM1_TAU ? k10 * em1_small(q1) : k11 - k10);
+        const float d0 = w * (__builtin_fabsf(q0) < EM1_TAU ? k00 * em1_small(q0) : k01 - k00);
+        const float w11 = w * k11, w01 = w * k01;
 #pragma unroll
         for (int q = 0; q < DP; ++q) {
           const float a0 = zv(k, t1, 0, q), a1 = zv(k, t1, 1, q), b0 = zv(k, t2, 0, q), b1 = zv(k, t2, 1, q);
-          g1[c][q] += k11 * (b1 - a1) - k10 * (b0 - a1);
-          g0[c][q] += k00 * (b0 - a0) - k01 * (b1 - a0);
+          g1[c][q] += __builtin_fmaf(d1, b0 - a1, w11 * (b1 - b0));
+          g0[c][q] -= __builtin_fmaf(d0, b0 - a0, w01 * (b1 - b0));
         }
       } else {
 #pragma unroll

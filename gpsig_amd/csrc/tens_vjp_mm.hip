@@ -5,8 +5,11 @@
 // G_i(t, t') = dLoss/dK_i and Gs = G_i(t, t') + G_i(t', t) (t as either argument), the weight of component c
 // at the pair is w_c = Gs prod_{c' != c} m_c'.  The gradient is a weighted sum over t' of the derivative of
 // m_c, which for the difference-of-RBF / linear components is linear in the points of t':
-//   RBF, increments   m = k(a1,b1) + k(a0,b0) - k(a1,b0) - k(a0,b1),  dk(a,b)/da = k(a,b) (b - a):
-//       dL/da1 = sum_t' w k11 b1 - w k10 b0 - a1 sum_t' (w k11 - w k10)      (and a0 alike)
+//   RBF, increments   m = k(a1,b1) + k(a0,b0) - k(a1,b0) - k(a0,b1),  dk(a,b)/da = k(a,b) (b - a), regrouped on
+//       db = b1 - b0 so that a short increment does not cancel (k11 (b1 - a1) and k10 (b0 - a1) agree to |db|
+//       of their size), with k11 - k10 = k10 expm1(<a1 - b0, db> - |db|^2/2) and k01 - k00 alike:
+//       dL/da1 =  sum_t' w (k11 - k10) b0 + w k11 db - a1 sum_t' w (k11 - k10)
+//       dL/da0 = -sum_t' w (k01 - k00) b0 - w k01 db + a0 sum_t' w (k01 - k00)
 //   RBF            m = k(a,b):  dL/da = sum_t' w m b - a sum_t' w m
 //   linear, incr.  m = <da, db>: dL/da1 = -dL/da0 = sum_t' w db
 //   linear         m = <a, b>:   dL/da = sum_t' w b
@@ -32,7 +35,7 @@ struct TgvArgs {
   const float *Z;  // (LT, T, zs), zs = d (points) or 2 d (point pairs)
   int T, d, zs, lt;
   float *m;        // (LT, T, T) component kernels
-  float *kv;       // RBF increments: (LT, 4, T, T) = k11, k10, k00, k01
+  float *kv;       // RBF increments: (LT, 4, T, T) = k11, k11 - k10, k01 - k00, k01
 };
 
 // mode: bit 0 = increments, bit 1 = RBF
@@ -134,11 +137,12 @@ __global__ __launch_bounds__(256) void tgv_pair_kernel(TgvArgs a) {
         } else {
           mv = (k11 - k10) - (k01 - k00);
         }
-        if (a.kv) {  // the VJP's corner kernels (the forward Gram needs m only)
+        if (a.kv) {  // the VJP's corner kernels and their differences along db (the forward Gram needs m only)
+          const float q1 = q + c;  // <a1 - b0, db> - |db|^2/2
           float *kv = a.kv + (long long)k * 4 * T2 + o;
           kv[0] = k11;
-          kv[T2] = k10;
-          kv[2 * T2] = k00;
+          kv[T2] = __builtin_fabsf(q1) < EM1_TAU ? k10 * em1_small(q1) : k11 - k10;
+          kv[2 * T2] = __builtin_fabsf(q) < EM1_TAU ? k00 * em1_small(q) : k01 - k00;
           kv[3 * T2] = k01;
         }
       } else if constexpr (RBF) {
@@ -157,7 +161,7 @@ struct TgwArgs {
 };
 
 // (B) the pair weights of level blockIdx.y + 1 and the coefficient matrices of its components; C:
-// RBF increments [w k11, -w k10, w k00, -w k01], RBF w m, linear w
+// RBF increments [w k11, w (k11 - k10), -w (k01 - k00), -w k01], RBF w m, linear w
 template <int MODE>
 __global__ __launch_bounds__(256) void tgv_weight_kernel(TgwArgs a) {
   constexpr bool INC = MODE & 1, RBF = (MODE & 2) != 0;
@@ -184,8 +188,8 @@ __global__ __launch_bounds__(256) void tgv_weight_kernel(TgwArgs a) {
     if constexpr (RBF && INC) {
       float *C = a.C + (long long)k * 4 * T2 + o;
       C[0] = w * C[0];
-      C[T2] = -w * C[T2];
-      C[2 * T2] = w * C[2 * T2];
+      C[T2] = w * C[T2];
+      C[2 * T2] = -w * C[2 * T2];
       C[3 * T2] = -w * C[3 * T2];
     } else if constexpr (RBF) {
       a.C[(long long)k * T2 + o] = w * m[c];
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(256) void tgv_weight_kernel(TgwArgs a) {
   }
 }
 
-// [Z_h | 1] (RBF), dZ (linear increments), Z (linear): P (LT, H, T, d + 1)
+// [Z | 1] (RBF), [Z_0 | 1] and [dZ | 0] (RBF increments), dZ (linear increments), Z (linear): P (LT, H, T, d + 1)
 __global__ __launch_bounds__(256) void tgv_points_kernel(const float *__restrict__ Z, int lt, int T, int d, int zs,
                                                          int H, int mode, float *__restrict__ P) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -209,8 +213,8 @@ __global__ __launch_bounds__(256) void tgv_points_kernel(const float *__restrict
   const int k = (int)(r / H);
   const float *z = Z + ((long long)k * T + t) * zs;
   float v;
-  if (q == d) v = (mode & 2) ? 1.0f : 0.0f;
-  else if (mode == 1) v = z[d + q] - z[q];  // linear increments: db
+  if (q == d) v = ((mode & 2) && h == 0) ? 1.0f : 0.0f;
+  else if (mode == 1 || h == 1) v = z[d + q] - z[q];  // db
   else v = z[h * d + q];
   P[idx] = v;
 }
@@ -343,7 +347,7 @@ int tens_gram_vjp_mm(const float *Z, int lt, int t, int incr, int d, int M, int 
                     G + (long long)hout * t * D1, D1, sP, lt, 0, 0, nullptr, 0);
   };
   if (mode == 3) {
-    // a1 side: w k11 [b1 | 1] - w k10 [b0 | 1];  a0 side: w k00 [b0 | 1] - w k01 [b1 | 1]
+    // a1 side: w k11 [db | 0] + w (k11 - k10) [b0 | 1];  a0 side: -w (k01 - k00) [b0 | 1] - w k01 [db | 0]
     if ((rc = mm(0, 1, 1, 0.0f)) || (rc = mm(1, 0, 1, 1.0f)) || (rc = mm(2, 0, 0, 0.0f)) || (rc = mm(3, 1, 0, 1.0f)))
       return rc;
   } else if ((rc = mm(0, 0, 0, 0.0f))) {

@@ -221,7 +221,7 @@ def test_pde_vjp(monkeypatch, l, d, dyadic):
 
 
 # ------------------------------------------------------------------------------------ inducing tensors, signatures
-@pytest.mark.parametrize("d", [3, 17])
+@pytest.mark.parametrize("d", [3, 12, 17])
 def test_tens_vs_seq(monkeypatch, d):
     from gpsig_amd import ops
     Z, X = tensors(M, 4, d, 40), walks(5, 8, d, 41)
