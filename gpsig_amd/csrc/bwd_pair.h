@@ -4,6 +4,11 @@
 #pragma once
 #include "sig_bwd.h"
 
+// rows per regenerated chunk of the VJPs (LDS: 4 waves x RC x 64 lanes x 2W floats)
+#ifndef GPSIG_WIDE_BWD_R
+#define GPSIG_WIDE_BWD_R 4
+#endif
+
 namespace gpsig {
 
 template <int M>

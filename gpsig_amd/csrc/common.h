@@ -262,6 +262,8 @@ GPSIG_DEV float wave_max(float v) {
 }
 
 // exp(x) = 2^(x log2 e) on the hardware transcendental unit (v_exp_f32, ~1 ulp).
-GPSIG_DEV float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+constexpr float L2E = 1.4426950408889634f;     // log2(e): exp(x) = exp2(x * L2E)
+constexpr float NHL2E = -0.72134752044448170f;  // -log2(e)/2: exp(-d2/2) = exp2(d2 * NHL2E)
+GPSIG_DEV float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * L2E); }
 
 }  // namespace gpsig

@@ -36,6 +36,11 @@
 #include "host.h"
 #include "sig_common.h"
 
+// corner floats per lane that a chunk of coarse steps may keep in registers (pde_chunk, PdeLayout::H)
+#ifndef GPSIG_PDE_HF
+#define GPSIG_PDE_HF 32
+#endif
+
 namespace gpsig {
 
 struct PdeBwdArgs {
@@ -69,9 +74,6 @@ GPSIG_DEV float tile_inc_b(const float *__restrict__ base, long long ld, int sub
 }
 
 // coarse steps per stored front: the chunk's K corners (H x REP x W <= GPSIG_PDE_HF floats per lane) live in registers
-#ifndef GPSIG_PDE_HF
-#define GPSIG_PDE_HF 32
-#endif
 template <int W, int REP>
 constexpr int pde_chunk() { return REP * W >= GPSIG_PDE_HF ? 1 : GPSIG_PDE_HF / (REP * W); }
 

@@ -200,26 +200,19 @@ GPSIG_DEV void wave_sum_last_n(float (&v)[N]) {
   group_incl_scan_n<64, N>(v);
 }
 
-#ifndef GPSIG_BWD_WPE
-#define GPSIG_BWD_WPE 1
-#endif
-// Timing ablations for tools/kbench_vjp.hip only (wrong results): bit 1 drops the per-row x-gradient
-// wave reduction and atomics, bit 2 the inversion scans, bit 4 the adjoint scans.
-#ifndef GPSIG_BWD_ABL
-#define GPSIG_BWD_ABL 0
-#endif
-template <int DP, int W, int LP, int M, int SEED>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_WPE))) void sig_bwd_kernel(BwdArgs p) {
-  constexpr int FS = feat_stride(DP);
-  constexpr int G = 64 / LP;
-  constexpr bool SEG = (64 % LP) != 0;  // LP = 20: 3 pairs per wave, lanes 60..63 idle (common.h)
-  constexpr bool DIFF = (SEED == SEED_RBF_DIFF || SEED == SEED_LIN_DIFF);  // else difference=False
-  constexpr bool RBF = (SEED == SEED_RBF_DIFF || SEED == SEED_RBF_POINT);   // base kernel
-  constexpr float NHL2E = -0.72134752044448170f;  // exp(-d2/2) = exp2(d2 * NHL2E)
-  constexpr float L2E = 1.4426950408889634f;
+// rows per chunk of the reverse sweep at W >= 4, LP != 20 (sig_bwd_kernel's RC)
 #ifndef GPSIG_BWD_RC
 #define GPSIG_BWD_RC 4
 #endif
+
+constexpr int BWD_WPE = 1;  // waves per SIMD the register allocation leaves room for
+template <int DP, int W, int LP, int M, int SEED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BWD_WPE))) void sig_bwd_kernel(BwdArgs p) {
+  constexpr int FS = feat_stride(DP);
+  constexpr int G = 64 / LP;
+  constexpr bool SEG = (64 % LP) != 0;  // LP = 20: 3 pairs per wave, lanes 60..63 idle (common.h)
+  constexpr bool DIFF = seed_is_diff(SEED);                                // else difference=False (no radial seeds here)
+  constexpr bool RBF = (SEED == SEED_RBF_DIFF || SEED == SEED_RBF_POINT);  // base kernel
   // rows per chunk of the reverse sweep (LDS: 4 waves x RC x 64 lanes x 2W floats per workgroup); the 20-lane
   // geometry (C2's 65-100 points) regenerates 6 rows per exact row: 21.73 -> 21.45 ms on tools/kbench_vjp.hip
   // (profiles/r6_vjp_rc_ab.txt), the other geometries keep 4 (round 3: 6 within noise there)
@@ -655,9 +648,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_W
       float t[DP];
 #pragma unroll
       for (int k = 0; k < DP; ++k) t[k] = RBF ? __builtin_fmaf(-s[DP], xi[k], s[k]) : s[k];
-      if constexpr (GPSIG_BWD_ABL & 1) {
-        if (t[0] == 1234.5f) gxa[pi] = t[1];  // keep the partials alive
-      } else if constexpr (BATCH) {
+      if constexpr (BATCH) {
         if (nslot == 0) pi0 = pi;
 #pragma unroll
         for (int k = 0; k < DP; ++k) tbuf[wave][nslot][k][lane] = t[k];
@@ -699,9 +690,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_W
           float cin[1], tot[1];
           cin[0] = cin_left ? ld_l2(tcar(blk) + (long long)i * ML + s - 1) : 0.0f;
           wave_excl_cols_carry_n<W, 1>(Cm, Sm, cin, tot);
-        } else if constexpr (GPSIG_BWD_ABL & 2) {
-#pragma unroll
-          for (int w = 0; w < W; ++w) Sm[0][w] = Cm[0][w];
         } else {
           group_excl_cols_n<LP, W, 1>(Cm, Sm);  // S_s(i) from the recovered C_s(i)
         }
@@ -732,11 +720,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWD_W
 #pragma unroll
             for (int m = 0; m < ML; ++m) ur[m] = uin[m] + tot[m];
           }
-        } else if constexpr (GPSIG_BWD_ABL & 4) {
-#pragma unroll
-          for (int m = 0; m < ML; ++m)
-#pragma unroll
-            for (int w = 0; w < W; ++w) r[m][w] = v[m][w];
         } else {
           group_rexcl_cols_n<LP, W, ML>(v, r);
         }
@@ -939,10 +922,7 @@ struct BwdGeo { int W, LP; };
 // DP <= 5, M <= 6.
 constexpr bool bwd_seg_ok(int DP, int M) { return DP >= 1 && DP <= 5 && M <= 6; }
 inline BwdGeo bwd_geometry(int l2, int DP, int M = 0) {
-#ifndef GPSIG_BWD_SEG
-#define GPSIG_BWD_SEG 1
-#endif
-  if (GPSIG_BWD_SEG && M > 0 && bwd_seg_ok(DP, M) && l2 > 64 && l2 <= 100) return {5, 20};
+  if (M > 0 && bwd_seg_ok(DP, M) && l2 > 64 && l2 <= 100) return {5, 20};
   const int W = DP <= 8 ? 4 : 2;
   for (int LP : {16, 32, 64})
     if (LP * W >= l2) return {W, LP};

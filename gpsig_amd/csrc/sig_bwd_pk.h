@@ -107,11 +107,9 @@ GPSIG_DEV void pk_excl_rexcl(f2 (&a)[W2], f2 (&b)[W2], const SF &sf) {
   }
 }
 
+constexpr int BWDPK_WPE = 2;  // waves per SIMD the register allocation leaves room for
 template <int DP, int W, int LP, int M, int SEED>
-#ifndef GPSIG_BWDPK_WPE
-#define GPSIG_BWDPK_WPE 2
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWDPK_WPE))) void sig_bwd_pk_kernel(BwdArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BWDPK_WPE))) void sig_bwd_pk_kernel(BwdArgs p) {
   static_assert(W % 2 == 0, "column pairs");
   static_assert(SEED == SEED_RBF_DIFF || SEED == SEED_LIN_DIFF, "difference seeds");
   constexpr int FS = feat_stride(DP);
@@ -119,8 +117,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPSIG_BWDPK
   constexpr int G = 64 / LP;
   constexpr bool SEG = (64 % LP) != 0;
   constexpr bool RBF = SEED == SEED_RBF_DIFF;
-  constexpr float NHL2E = -0.72134752044448170f;  // exp(-d2/2) = exp2(d2 * NHL2E)
-  constexpr float L2E = 1.4426950408889634f;
   constexpr int RC = 4;  // rows per regenerated chunk (RbfSeed cells), LDS: 4 waves x RC x W x 64 f2
   constexpr int ML = M > 1 ? M - 1 : 1;
   __shared__ __attribute__((aligned(16))) f2 cbuf[RBF ? 4 : 1][RBF ? RC : 1][W][64];

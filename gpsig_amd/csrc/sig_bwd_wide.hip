@@ -83,7 +83,6 @@ __global__ __launch_bounds__(256) void wide_diag_anchor_kernel(const float *__re
       qq[g] = __builtin_fmaf(df, dxj, qq[g]);
     }
   }
-  constexpr float NHL2E = -0.72134752044448170f, L2E = 1.4426950408889634f;
 #pragma unroll
   for (int g = 0; g < ANCHOR_G; ++g) {
     const int t = t0 + g;

@@ -6,6 +6,13 @@
 
 #include "common.h"
 
+// Rows between exact re-evaluations of the packed RBF seeds' row recurrences (RbfSeedPk::ANCHOR here, the wide
+// seed in wide.h, the matrix-core Gram in sig_fo_mf.h).  64 -> 128 (profiles/r6_anchor128_ab.txt, N = 2048): H
+// 22.43 -> 22.01 ms, C5 26.54 -> 26.16 ms; headline max-abs error 7.9e-7 -> 9.1e-7.
+#ifndef GPSIG_PK_ANCHOR
+#define GPSIG_PK_ANCHOR 128
+#endif
+
 namespace gpsig {
 
 // Per-point feature record, FS floats (16-byte aligned): [x (DP) | dx (DP) | |dx|^2/2 | g | pad...]
@@ -112,12 +119,8 @@ struct RowData {
 template <int DP, int W, int SEED>
 struct RowSeed {
   static constexpr int FS = feat_stride(DP);
-  static constexpr bool DIFF = (SEED == SEED_RBF_DIFF || SEED == SEED_LIN_DIFF);
-#ifndef GPSIG_D2_RECUR
-#define GPSIG_D2_RECUR 1
-#endif
+  static constexpr bool DIFF = seed_is_diff(SEED);  // (the radial seeds go to RadialSeed)
   static constexpr int ANCHOR = 8;  // exact |x_i - y_j|^2 every ANCHOR rows (d^2 row recurrence between)
-  static constexpr float NHL2E = -0.72134752044448170f;  // -log2(e)/2: exp(-d2/2) = exp2(d2 * NHL2E)
   float y[W][DP], dy[W][DP], hdy[W];
   bool valid_last;  // column W-1 of this lane is a real cell (others: exact zeros by construction)
   bool valid[W];    // POINT seeds
@@ -187,9 +190,9 @@ struct RowSeed {
 #pragma unroll
         for (int k = 0; k < DP; ++k) {
           diff[w][k] = rd.x[k] - y[w][k];
-          if constexpr (ANCH || !GPSIG_D2_RECUR) s = __builtin_fmaf(diff[w][k], diff[w][k], s);
+          if constexpr (ANCH) s = __builtin_fmaf(diff[w][k], diff[w][k], s);
         }
-        d2[w] = (ANCH || !GPSIG_D2_RECUR) ? s : __builtin_fmaf(-2.0f, pp[w], d2[w]);
+        d2[w] = ANCH ? s : __builtin_fmaf(-2.0f, pp[w], d2[w]);
         kn[w] = __builtin_amdgcn_exp2f(d2[w] * NHL2E);
       }
       const float knR = lane_next(kn[0]);
@@ -301,7 +304,6 @@ struct RadialSeed {
   static constexpr int FS = feat_stride(DP);
   static constexpr bool DIFF = SEED == SEED_RAD_DIFF;
   static constexpr int ANCHOR = 1 << 30;  // no row recurrence
-  static constexpr float L2E = 1.4426950408889634f;
   float y[W][DP];
   bool valid_last;  // DIFF: column W-1 of this lane is a real cell
   bool valid[W];    // POINT
@@ -402,32 +404,19 @@ using GenSeed = std::conditional_t<seed_is_radial(SEED), RadialSeed<DP, W, SEED>
 // rounding drift is bounded by ANCHOR steps.  When |p| or |c| of some cell of the wave reaches
 // EM1_TAU (a wave-uniform branch), the next row is evaluated exactly and those cells take the plain
 // corner difference of the k grid.
-#ifndef GPSIG_NAIVE
-#define GPSIG_NAIVE 1
-#endif
-#ifndef GPSIG_P0CHECK
-#define GPSIG_P0CHECK 1
-#endif
 template <int DP, int W>
 struct RbfSeedPk {
   static_assert(W % 2 == 0, "column pairs");
   static constexpr int W2 = W / 2;
   static constexpr int FS = feat_stride(DP);
-#ifndef GPSIG_PK_ANCHOR
-#define GPSIG_PK_ANCHOR 128
-#endif
   static constexpr int ANCHOR = GPSIG_PK_ANCHOR;
-  static constexpr float NHL2E = -0.72134752044448170f;  // exp(-d2/2) = exp2(d2 * NHL2E)
-  static constexpr float L2E = 1.4426950408889634f;
-  // Wide channels (DP >= GPSIG_YG_DP): only column pair 0's points stay in registers (the rows' p dots
+  // Wide channels (DP >= YG_DP): only column pair 0's points stay in registers (the rows' p dots
   // need them, the other pairs' p follow by the column recurrence); the others are needed only on
   // anchor and slow rows (exact) and are re-read from the records there.  This keeps W = 8 columns per
   // lane within 256 VGPRs at D = 6..8.
-#ifndef GPSIG_YG_DP
-#define GPSIG_YG_DP 6
-#endif
+  static constexpr int YG_DP = 6;
   // (W = 10, the 10-lane groups: also at any DP, to stay within 256 VGPRs)
-  static constexpr bool YG = DP >= GPSIG_YG_DP || W > 8;
+  static constexpr bool YG = DP >= YG_DP || W > 8;
   static constexpr int YR = YG ? 1 : W2;
   f2 y[YR][DP], dy[W2][DP], hdy[W2];
   f2 Eq[W2], kc[W2];  // expm1(q_ij), k(x_i, y_j)
@@ -601,7 +590,7 @@ struct RbfSeedPk {
         // CLO: every Ec is in the cubic's range a priori, and the pairs after the first take Ep by the exact
         // chain Ep' = Ep + (1 + Ep) Ec, so only the first pair's p meets a polynomial
         if constexpr (CLO) {
-          if (w2 == 0 || !GPSIG_P0CHECK) mx = __builtin_fmaxf(mx, __builtin_fabsf(p[w2][h]));
+          if (w2 == 0) mx = __builtin_fmaxf(mx, __builtin_fabsf(p[w2][h]));
         } else {
           mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
         }
@@ -619,7 +608,7 @@ struct RbfSeedPk {
   GPSIG_DEV bool row_hot(const Row &rd, f2 p0, f2 (&dM)[W2]) {
     f2 p[W2], c[W2], Ec[W2], Ep[W2];
     const float mx = cells<CLO>(rd, p0, p, c, Ec, Ep, dM);
-    if (GPSIG_NAIVE && __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0) return true;
+    if (__builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0) return true;
 #pragma unroll
     for (int w2 = 0; w2 < W2; ++w2) {
       // Eq + Ec is a rounded sum: Ec's final product x P(x) is not contracted into it
@@ -639,31 +628,12 @@ struct RbfSeedPk {
   // and (1 + Ep) Ec is a term the cell needs anyway.  Only column pair 0 (the lane's columns 0 and
   // W/2) takes the dot and the polynomial; pairs 1 .. W/2-1 follow in-lane (two operations each instead
   // of D + 6).  Rows with a cell outside the polynomial range re-evaluate every Ep directly (slow path).
-#ifndef GPSIG_PCHAIN
-#define GPSIG_PCHAIN 1
-#endif
   // CLO: the pair block's |c| bound holds (bound_c): Ec by the cubic, and only |p| is range-checked.
   template <bool CLO = false>
   GPSIG_DEV void row(const Row &rd, bool anch, f2 (&dM)[W2]) {
-    f2 p[W2], c[W2];
-    if constexpr (!GPSIG_PCHAIN) {  // A/B arm: every pair's dots and polynomials evaluated directly
-#pragma unroll
-      for (int w2 = 0; w2 < W2; ++w2) {
-        f2 a = splat2(-rd.g), cc = splat2(0.0f);
-#pragma unroll
-        for (int k = 0; k < DP; ++k) {
-          a = fma2(yv(w2, k), splat2(rd.dx[k]), a);
-          cc = fma2(dy[w2][k], splat2(rd.dx[k]), cc);
-        }
-        p[w2] = a;
-        c[w2] = cc;
-      }
-      row_pc(rd, anch, p, c, dM);
-      return;
-    }
-    f2 Ec[W2], Ep[W2];
+    f2 p[W2], c[W2], Ec[W2], Ep[W2];
     const float mx = cells<CLO>(rd, p0_dot(rd), p, c, Ec, Ep, dM);
-    const bool slow = GPSIG_NAIVE && __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
+    const bool slow = __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
     if (anch || slow) {
       f2 Eqn[W2], kn[W2];
       next_exact(rd, Eqn, kn);
@@ -751,7 +721,7 @@ struct RbfSeedPk {
 #pragma unroll
       for (int h = 0; h < 2; ++h) mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
     }
-    const bool slow = GPSIG_NAIVE && __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
+    const bool slow = __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
     if (anch || slow) next_exact(rd, Eqn, kn);
     const float knR = lane_next(kn[0][0]);
     if (slow) {

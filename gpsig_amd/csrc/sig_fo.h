@@ -28,18 +28,6 @@ namespace gpsig {
 #endif
 constexpr int WIDE_R = GPSIG_WIDE_R;
 
-// DIAGK: the diagonal pass (pairs (a, a)) is the same body under its own symbol, so profiler
-// statistics of the Gram launch are not mixed with it.  SAVE: also write the VJP's saved state
-// (gpsig_sig_gram_state) -- a separate instantiation, so the plain Gram keeps its register budget.
-// MF: the increment inner products of the RBF seed on the matrix cores (RbfSeedPk::mfma_pc), 4 rows
-// per batch, instead of packed VALU dots.
-// SPLIT (diagnostic, SURVEY.md 8d "split design"): 1 = producer (cells dM of every row to p.dmbuf, no
-// recursion, no output), 2 = consumer (cells streamed from p.dmbuf through the recursion and epilogue).
-// Waves per SIMD the register allocation must leave room for: 2 (256 VGPRs) where W = 8 columns per lane
-// only just fit at D = 7..8 (the allocator would otherwise take 260 and run one wave per SIMD, 1.6x
-// slower; at 256 it spills a few registers outside the row loop), and for the packed RBF seed at W = 8,
-// M <= 6 at every D: its row loop (runs of hot rows, below) takes 259 at D = 5, M = 5 left to itself, where
-// the former loop fitted 230.  Everything else is compiled as it was.
 // per-row record type of the row loop: the seed's own (wide, packed RBF) or the generic RowData
 template <bool WIDE, bool PK, class PS, int DP, int W>
 struct FoRec { using type = RowData<DP>; };
@@ -48,19 +36,26 @@ struct FoRec<true, PK, PS, DP, W> { using type = typename PS::Row; };
 template <class PS, int DP, int W>
 struct FoRec<false, true, PS, DP, W> { using type = typename RbfSeedPk<DP, W>::Row; };
 
+// Waves per SIMD the register allocation must leave room for: 2 (256 VGPRs) where W = 8 columns per lane
+// only just fit at D = 7..8 (the allocator would otherwise take 260 and run one wave per SIMD, 1.6x
+// slower; at 256 it spills a few registers outside the row loop), and for the packed RBF seed at W = 8,
+// M <= 6 at every D: its row loop (runs of hot rows, below) takes 259 at D = 5, M = 5 left to itself, where
+// the former loop fitted 230.  Everything else is compiled as it was.
 __host__ __device__ constexpr int fo_waves(int DP, int W, int M, int SEED) {
   const bool pk8 = SEED == SEED_RBF_DIFF && W == 8 && DP >= 1 && M <= 6;
   // (the radial seeds keep their row state beside the column points: the whole register file, no spills)
   return ((W == 8 && DP > 6 && M <= 6 && !seed_is_radial(SEED)) || W == 10 || pk8) ? 2 : 1;
 }
 
+// DIAGK: the diagonal pass (pairs (a, a)) is the same body under its own symbol, so profiler
+// statistics of the Gram launch are not mixed with it.  SAVE: also write the VJP's saved state
+// (gpsig_sig_gram_state) -- a separate instantiation, so the plain Gram keeps its register budget.
+// MF: the increment inner products of the RBF seed on the matrix cores (RbfSeedPk::mfma_pc), 4 rows
+// per batch, instead of packed VALU dots.
+// SPLIT (diagnostic, SURVEY.md 8d "split design"): 1 = producer (cells dM of every row to p.dmbuf, no
+// recursion, no output), 2 = consumer (cells streamed from p.dmbuf through the recursion and epilogue).
 template <int DP, int W, int LP, int M, int SEED, bool DIAGK, bool SAVE = false, bool MF = false, int SPLIT = 0>
-#ifdef GPSIG_FO_LB
-#define GPSIG_FO_BOUNDS __launch_bounds__(256, GPSIG_FO_LB)
-#else
-#define GPSIG_FO_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP, W, M, SEED))))
-#endif
-__global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP, W, M, SEED)))) void sig_fo_kernel(SigArgs p) {
   // DP == 0: wide channel counts (runtime p.wd, channel-major records, wide.h)
   constexpr bool WIDE = DP == 0;
   constexpr bool DIFF = seed_is_diff(SEED);
@@ -148,11 +143,8 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
       seed.init(p.wd, p.lw1, p.lw2, fx, fy + j0, gl, npts);
     else
       seed.init(fx, fy + (long long)j0 * FS, gl, npts);
-#ifndef GPSIG_CLO
-#define GPSIG_CLO 1
-#endif
-    if constexpr (PK && !MF && SPLIT != 2 && GPSIG_CLO) seed.bound_c(fx, nrows);
-    if constexpr (WIDE && SEED == SEED_RBF_DIFF && GPSIG_CLO) seed.bound_c(nrows);
+    if constexpr (PK && !MF && SPLIT != 2) seed.bound_c(fx, nrows);
+    if constexpr (WIDE && SEED == SEED_RBF_DIFF) seed.bound_c(nrows);
     // DIAG: the pair's seed tiles (wide.h DiagTiles) replace the chunk dots' and the anchors' channel loops
     bool tiled = false;
     if constexpr (WIDE && SEED == SEED_RBF_DIFF && DIAGK) {
@@ -315,7 +307,7 @@ __global__ GPSIG_FO_BOUNDS void sig_fo_kernel(SigArgs p) {
           if constexpr (WIDE_R > 7) one(std::integral_constant<int, 7>{});
         }
       } else {
-      if constexpr (PK && !MF && SPLIT != 2 && GPSIG_PCHAIN) {
+      if constexpr (PK && !MF && SPLIT != 2) {
         // Runs of hot rows (RbfSeedPk::row_hot: no exact evaluation in the body, so kc, Eq and kcR are
         // advanced in their registers), each ended by the row that needs the exact path: the anchor row, or
         // a row with a cell outside the polynomial range, which leaves the run before any state is written
@@ -472,10 +464,7 @@ inline Geo fo_geometry(int l2, int DP, int M, bool mf = false, int seed = -1) {
       if (LP * 4 >= l2) return {4, LP};
     return {0, 0};
   }
-#ifndef GPSIG_FO_SEG
-#define GPSIG_FO_SEG 1
-#endif
-  if (GPSIG_FO_SEG && fo_seg_ok(DP, M, seed) && l2 > 64 && l2 <= 100) return {10, 10};
+  if (fo_seg_ok(DP, M, seed) && l2 > 64 && l2 <= 100) return {10, 10};
   // smallest LP (shortest scans) at which some W <= fo_wmax covers the sequence, smallest such W
   for (int LP : {16, 32, 64})
     for (int W = 2; W <= fo_wmax(DP, M); W *= 2)

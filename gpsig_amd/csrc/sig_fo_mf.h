@@ -159,7 +159,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4)
   constexpr bool RBF = SEED == SEED_RBF_DIFF;
   constexpr int LP = MF_LP, W2 = W / 2, LPW = LP * W, NCB = LPW / 16, ML = M > 1 ? M - 1 : 1;
   constexpr int LDC = LPW + 4;
-  constexpr float L2E = 1.4426950408889634f;
   constexpr int ANCH = GPSIG_PK_ANCHOR;
   constexpr int XB = NW * MF_G;  // x-sequences per workgroup
   constexpr int CPB = LPW - 1;   // cells per column block
@@ -487,7 +486,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4)
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             if constexpr (CLO) {  // only the first pair's p meets a polynomial (RbfSeedPk::row)
-              if (w2 == 0 || !GPSIG_P0CHECK) mx = __builtin_fmaxf(mx, __builtin_fabsf(pv[w2][h]));
+              if (w2 == 0) mx = __builtin_fmaxf(mx, __builtin_fabsf(pv[w2][h]));
             } else {
               mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(pv[w2][h])), __builtin_fabsf(c[w2][h]));
             }

@@ -27,10 +27,6 @@
 
 namespace gpsig {
 
-#ifndef GPSIG_WIDE_BWD_R
-#define GPSIG_WIDE_BWD_R 4
-#endif
-
 // f(std::integral_constant<int, k>) for k = B .. E-1 (ascending) / E-1 .. B (descending)
 template <int B, int E, class F>
 GPSIG_DEV void static_for(F &&f) {

@@ -20,6 +20,11 @@
 #pragma once
 #include "sig_ho_bwd.h"
 
+// slab slots (multipliers + column sums) up to which the W = 4 kernel runs without LDS fences (FENCE below)
+#ifndef HO_LDS_NOFENCE_SLOTS
+#define HO_LDS_NOFENCE_SLOTS 100  // 99 slots (order 5 at 6 levels, 4 at 7) run unfenced without spills; 111 (order 6) spill
+#endif
+
 namespace gpsig {
 
 template <int ORD, int M>
@@ -31,9 +36,6 @@ constexpr size_t ho_bwd_lds_slab_bytes() {
 }
 constexpr size_t ho_bwd_lds_cbuf_bytes(int W) { return (size_t)GPSIG_WIDE_BWD_R * 64 * 2 * W * sizeof(float); }
 
-#ifndef HO_LDS_NOFENCE_SLOTS
-#define HO_LDS_NOFENCE_SLOTS 100  // 99 slots (order 5 at 6 levels, 4 at 7) run unfenced without spills; 111 (order 6) spill
-#endif
 template <int ORD, int M, int W, int SEED>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) void sig_ho_bwd_lds_kernel(BwdArgs p) {
   constexpr int W2 = W / 2;

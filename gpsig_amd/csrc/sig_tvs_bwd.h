@@ -59,8 +59,6 @@ __device__ __forceinline__ void tvs_bwd_level(const TvsBwdArgs &a,
   constexpr int LT = I;
   constexpr int NW = tvs_bwd_waves<DP, INCR>();
   constexpr int KB = I * (I - 1) / 2;  // first component of the level
-  constexpr float NHL2E = -0.72134752044448170f;  // exp(-d2/2) = exp2(d2 * NHL2E)
-  constexpr float L2E = 1.4426950408889634f;
   const int lane = threadIdx.x & 63;
   const int wave = wave_uniform(threadIdx.x >> 6);
   const int n = a.n, d = a.d, FC = 2 * d + 3, T = a.t, L = a.l;

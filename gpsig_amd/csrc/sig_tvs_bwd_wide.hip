@@ -63,7 +63,6 @@ __device__ __forceinline__ void tvsw_level(const TvsBwdWideArgs &a) {
   constexpr int LTM = MMAX * (MMAX + 1) / 2;
   constexpr int H = (RBF && INCR) ? 2 : 1;
   constexpr int ANCHOR = 32;
-  constexpr float NHL2E = -0.72134752044448170f, L2E = 1.4426950408889634f;
   const int lane = threadIdx.x;
   const int tt = blockIdx.y;
   const int n = a.n, d = a.d, FC = 2 * d + 3, T = a.t, L = a.l, LT = a.lt;

@@ -16,6 +16,11 @@
 #include "gemm.h"
 #include "internal.h"
 
+// cells between exact re-evaluations of k (and Ep), both kernels of this file
+#ifndef GPSIG_TVS_ANCHOR
+#define GPSIG_TVS_ANCHOR 32
+#endif
+
 namespace gpsig {
 
 struct TvsPkArgs {
@@ -56,22 +61,14 @@ __global__ __launch_bounds__(256) void tvs_prep_kernel(const float *__restrict__
   }
 }
 
+// waves per SIMD the register allocation leaves room for: increments, points
+constexpr int TVS_WPE = 2, TVS_WPE0 = 1;
 template <int DP, int M, bool INCR>
-#ifndef GPSIG_TVS_WPE
-#define GPSIG_TVS_WPE 2
-#endif
-#ifndef GPSIG_TVS_WPE0
-#define GPSIG_TVS_WPE0 1
-#endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INCR ? GPSIG_TVS_WPE : GPSIG_TVS_WPE0))) void tvs_pk_kernel(TvsPkArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INCR ? TVS_WPE : TVS_WPE0))) void tvs_pk_kernel(TvsPkArgs a) {
   constexpr int LT = M * (M + 1) / 2;
   constexpr int ZS = tvs_zs<DP, INCR>();
-#ifndef GPSIG_TVS_ANCHOR
-#define GPSIG_TVS_ANCHOR 32
-#endif
   constexpr int ANCHOR = GPSIG_TVS_ANCHOR;
   constexpr float TVS_CORNER = 2.0f;  // |q| or |c| past this: corner form (increments)
-  constexpr float NHL2E = -0.72134752044448170f, L2E = 1.4426950408889634f;
   const int lane = threadIdx.x;
   const int tt = blockIdx.y;
   // instantiated per exact channel count (DP == a.d): no per-channel guards in the time loop
@@ -438,7 +435,6 @@ template <int M, bool INCR, bool RBF>
 __global__ __launch_bounds__(64) void tvs_wide_kernel(TvsWideArgs a) {
   constexpr int LT = M * (M + 1) / 2;
   constexpr float TVS_CORNER = 2.0f;
-  constexpr float NHL2E = -0.72134752044448170f, L2E = 1.4426950408889634f;
   constexpr int ANCHOR = GPSIG_TVS_ANCHOR;
   constexpr int H = (RBF && INCR) ? 2 : 1;
   const int lane = threadIdx.x;

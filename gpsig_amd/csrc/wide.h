@@ -93,8 +93,6 @@ struct RbfSeedWide {
   static_assert(W == 2 || W == 4 || W == 8, "columns per lane");
   static constexpr int W2 = W / 2;
   static constexpr int ANCHOR = GPSIG_PK_ANCHOR;
-  static constexpr float NHL2E = -0.72134752044448170f;
-  static constexpr float L2E = 1.4426950408889634f;
   int d, lw, lwx;  // channel count, record stride of the y (column) and x (row) sequences
   cfloat *fx;         // row side: the x-sequence's record (wave-uniform, scalar loads)
   const float *fyc;   // column side: the y-sequence's record at this lane's first column
@@ -346,7 +344,6 @@ struct WideSeedGen {
   static constexpr int W2 = W / 2;
   static constexpr int ANCHOR = 1 << 30;
   static constexpr bool DIFF = SEED == SEED_LIN_DIFF;
-  static constexpr float NHL2E = -0.72134752044448170f;
   int d, lw, lwx;  // channel count, record stride of the y (column) and x (row) sequences
   cfloat *fx;
   const float *fyc;
@@ -439,7 +436,6 @@ struct RadialSeedWide {
   static constexpr int W2 = W / 2;
   static constexpr int ANCHOR = 1 << 30;
   static constexpr bool DIFF = SEED == SEED_RAD_DIFF;
-  static constexpr float L2E = 1.4426950408889634f;
   int d, lw, lwx;
   cfloat *fx;
   const float *fyc;

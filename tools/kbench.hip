@@ -1,6 +1,6 @@
 // A/B timing harness for the first-order Gram kernel (one instantiation), independent of the ABI.
-// Build variants with -D flags (GPSIG_FO_BLOCKED, GPSIG_D2_RECUR, GPSIG_FO_LB) and compare in one
-// gpurun call:  ./kbench N reps  ->  prints "variant ms_per_launch entries_per_s"
+// Build variants with -D flags (the shape: KD, KM, KL, KW, KLP, KMF; the kernel's tunable GPSIG_PK_ANCHOR) and
+// compare them in one GPU job:  ./kbench N reps  ->  prints "variant ms_per_launch entries_per_s"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
