@@ -52,6 +52,10 @@ int pde_launch_tiled(const float *X, int n1, int l1, const float *Y, int n2, int
                      int pair_mode, int row_begin, int row_end, float *out, int out_row0, int out_rows,
                      long long out_ld, void *scratch, size_t scratch_bytes, hipStream_t s);
 bool pde_tiled(int d, int dyadic);
+// channel instantiation of the fixed PDE kernels, forward and adjoint (0: none, the increment tiles)
+inline int pde_dp(int d) { return d <= 8 ? d : (d <= 16 ? 16 : 0); }
+// gpsig_pde_route's forward half: out[0..6] = family, DP, REP, W, LP, column blocks, sub (include/gpsig_amd.h)
+int pde_fwd_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode, int *out);
 void pde_tile_chunk(int n1, int l1, int n2, int l2, int pair_mode, int &rows, long long &cols);
 size_t pde_tile_scratch_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode);
 int increments_launch(const float *X, int n, int l, int d, float *dX, hipStream_t s);

@@ -410,11 +410,14 @@ inline double pde_cost(int IC, int J, int REP, int DP, int W, int G) {
   const int U = (J + W - 1) / W;
   return (double)(IC + U - 1) * (3.0 * REP * W + (DP / 2.0 + 7.0) * W / REP + 2.0 * REP + 12.0) / G;
 }
-inline int pde_w64(int J, int REP) {  // W of pde_rep_w's one-pair-per-wave geometry
+// W of the one-pair-per-wave geometry (pde_rep_w dispatches on it): the smallest multiple of REP with J / W <= 64
+// lanes.  Longer grids run in column blocks of 64 W fine columns: W = 4 REP for REP <= 4, 16 for REP = 8 and 16
+// (dyadic 3 and 4).
+inline int pde_w64(int J, int REP) {
   if (J <= 64 * REP) return REP;
   if (J <= 128 * REP && 2 * REP <= 16) return 2 * REP;
   if (REP <= 4 && J <= 192 * REP) return 3 * REP;
-  return 4 * REP;
+  return REP <= 4 ? 4 * REP : 16;
 }
 inline PdeLp pde_pick_lp(int IC, int J, int REP, int DP) {
   static const int force = env_int("GPSIG_PDE_LP", 0);
@@ -454,16 +457,17 @@ static int pde_lp_dispatch(const PdeArgs &a, long long nblocks, PdeLp g, hipStre
   return GPSIG_EUNSUPPORTED;
 }
 
-// W = the smallest multiple of REP with J / W <= 64 lanes (-1: use the per-row kernel).  Longer grids run
-// in column blocks of 64 W fine columns: W = 4 REP for REP <= 4, 16 for REP = 8 and 16 (dyadic 3 and 4).
+// W = pde_w64(J, REP) (-1: use the per-row kernel; no shape gets there, see launch_pde_rep: W / REP <= 4 and
+// DP <= 16).
 template <typename T, int DP, int REP>
 static int pde_rep_w(const PdeArgs &a, long long nblocks, int J, hipStream_t s) {
-  if (J <= 64 * REP) return launch_pde_rep<T, DP, REP, REP>(a, nblocks, s);
-  if (J <= 128 * REP && 2 * REP <= 16) return launch_pde_rep<T, DP, (2 * REP <= 16 ? 2 * REP : REP), REP>(a, nblocks, s);
-  if (REP <= 4 && J <= 192 * REP) return launch_pde_rep<T, DP, (REP <= 4 ? 3 * REP : REP), REP>(a, nblocks, s);
-  if (REP <= 4 && J <= 256 * REP) return launch_pde_rep<T, DP, (REP <= 4 ? 4 * REP : REP), REP>(a, nblocks, s);
-  // longer: column blocks of 256 * REP fine columns (REP <= 4) or 1024 (REP 8, 16)
+  const int W = pde_w64(J, REP);
+  if (W == REP) return launch_pde_rep<T, DP, REP, REP>(a, nblocks, s);
+  if (W == 2 * REP && 2 * REP <= 16) return launch_pde_rep<T, DP, (2 * REP <= 16 ? 2 * REP : REP), REP>(a, nblocks, s);
+  if (REP <= 4 && W == 3 * REP) return launch_pde_rep<T, DP, (REP <= 4 ? 3 * REP : REP), REP>(a, nblocks, s);
+  // 4 REP: up to 256 * REP fine columns in one block, longer grids in column blocks of that many
   if (REP <= 4) return launch_pde_rep<T, DP, (REP <= 4 ? 4 * REP : REP), REP>(a, nblocks, s);
+  // REP 8, 16: column blocks of 1024 fine columns
   if (REP <= 16) return launch_pde_rep<T, DP, 16, (REP <= 16 ? REP : 16)>(a, nblocks, s);
   return -1;
 }
@@ -513,17 +517,44 @@ static int pde_w(const PdeArgs &a, long long nblocks, int J, PdeLp g, hipStream_
   }
 }
 
+// the forward's grid past the kernels' refinement: tile cells split 2^sub ways (pde_rep_w takes up to 16)
+static int pde_fwd_sub(int dyadic) { return dyadic > 4 ? dyadic - 4 : 0; }
+
+// lane groups of Gram pairs: solver 1, dyadic <= 2, d <= 8 (pde_pick_lp); {64, 0}: one pair per wave
+static PdeLp pde_lane_group(bool tile, int l1, int l2, int d, int dyadic, int solver, int pair_mode) {
+  PdeLp lpg{64, 0};
+  if (!tile && pair_mode != GPSIG_PAIRS_DIAG && solver == 1 && dyadic <= 2 && d <= 8 && l1 >= 2 && l2 >= 2)
+    lpg = pde_pick_lp(l1 - 1, (1 << dyadic) * (l2 - 1), 1 << dyadic, pde_dp(d));
+  return lpg;
+}
+
+// gpsig_pde_route, forward: the choices of gpsig_pde_gram_ex -> pde_launch / pde_launch_tiled -> pde_launch_args
+// -> pde_w, by the helpers they call
+int pde_fwd_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode, int *out) {
+  const bool tile = pde_tiled(d, dyadic);
+  const int sub = tile ? pde_fwd_sub(dyadic) : 0;
+  const PdeLp g = pde_lane_group(tile, l1, l2, d, dyadic, solver, pair_mode);
+  const int REP = 1 << (dyadic - sub);
+  const long long J = (long long)(1 << dyadic) * (l2 - 1);
+  if (J > (1LL << 30)) return GPSIG_EUNSUPPORTED;
+  const int W = g.LP != 64 ? g.W : pde_w64((int)J, REP);
+  out[0] = tile ? 2 : (g.LP != 64 ? 1 : 0);
+  out[1] = tile ? 0 : pde_dp(d);
+  out[2] = REP;
+  out[3] = W;
+  out[4] = g.LP;
+  out[5] = (int)((J + (long long)g.LP * W - 1) / ((long long)g.LP * W));  // pde_rep_kernel's nblk
+  out[6] = sub;
+  return GPSIG_OK;
+}
+
 // a: inputs, mode, rows and output filled; a.inc != nullptr selects the increment-tile kernels (DP == 0)
 static int pde_launch_args(PdeArgs a, hipStream_t s) {
   const int n2 = a.n2, l1 = a.l1, l2 = a.l2, d = a.d, dyadic = a.dyadic, solver = a.solver;
   const int pair_mode = a.pair_mode, row_begin = a.row_begin, row_end = a.row_end;
   const bool tile = a.inc != nullptr;
   const int J = (1 << dyadic) * (l2 - 1);
-  const int DPI = d <= 8 ? d : 16;
-  // lane groups of Gram pairs: solver 1, dyadic <= 2, d <= 8 (pde_pick_lp)
-  PdeLp lpg{64, 0};
-  if (!tile && pair_mode != GPSIG_PAIRS_DIAG && solver == 1 && dyadic <= 2 && d <= 8 && l1 >= 2 && l2 >= 2)
-    lpg = pde_pick_lp(l1 - 1, J, 1 << dyadic, DPI);
+  const PdeLp lpg = pde_lane_group(tile, l1, l2, d, dyadic, solver, pair_mode);
   PairTiles t;
   const int trc = pair_tiles(pair_mode, row_begin, row_end, n2, 64 / lpg.LP, &t);
   a.ntb = t.ntb;
@@ -534,7 +565,7 @@ static int pde_launch_args(PdeArgs a, hipStream_t s) {
   if (trc) return trc;
   using T = double;  // fp64 solution grid (the reference's float64), fp32 increments (as the CUDA op, .cu:27)
   if (tile) return pde_w<T, 0>(a, nblocks, J, lpg, s);
-  return dispatch<1, 2, 3, 4, 5, 6, 7, 8, 16>(d <= 8 ? d : (d <= 16 ? 16 : 0), [&](auto dp) {
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8, 16>(pde_dp(d), [&](auto dp) {
     return pde_w<T, decltype(dp)::value>(a, nblocks, J, lpg, s);
   });
 }
@@ -618,7 +649,7 @@ int pde_tiled_run(PdeArgs a, void *scratch, size_t scratch_bytes, hipStream_t s,
   if (rc) return rc;
   if (pm == GPSIG_PAIRS_RECT && (rc = increments_launch(a.Y, n2, l2, d, dY, s))) return rc;
   // kernel grid: 2^(dyadic - sub) fine cells per tile cell and direction (pde_rep_w takes up to 16)
-  a.sub = a.dyadic > 4 ? a.dyadic - 4 : 0;
+  a.sub = pde_fwd_sub(a.dyadic);
   a.inc = T;
   const int rb0 = a.row_begin, rb1 = a.row_end;
   for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += rows) {

@@ -73,6 +73,44 @@ extern "C" size_t gpsig_pde_vjp_workspace_bytes(int npairs, int l1, int l2, int 
   return (size_t)npairs * (size_t)pde_front_floats(l1, l2, dyadic) * sizeof(float);
 }
 
+// pairs per workgroup of the adjoint kernels: 4 unless the per-wave LDS (row accumulators and dx of x) of long x
+// needs fewer; mode as pde_adj_impl's
+static int pde_adj_wpb(int l1, int l2, int d, int dyadic, int pair_mode, int mode) {
+  if (pde_bwd_tiled(d, dyadic)) return 4;  // no per-wave LDS on tiles
+  const int dp = pde_dp(d);
+  int wpb = 4;
+  // cross pairs also keep their lanes' column sums in LDS (W / REP coarse columns per lane)
+  const int wc = pair_mode == GPSIG_PAIRS_RECT && mode != 1 ? pde_layout(l1, l2, dyadic).W >> dyadic : 0;
+  while (wpb > 1 && (size_t)wpb * pde_lds_wave_doubles(l1 - 1, dp, wc) * sizeof(double) > 160 * 1024) wpb /= 2;
+  return wpb;
+}
+
+// gpsig_pde_route: what pde_adj_impl / pde_adj_tiled / pde_adj_rep would choose (the forward: pde_fwd_route,
+// pde.hip); no launch, no device
+extern "C" int gpsig_pde_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode, int adjoint, int *out) {
+  if (!out || l1 < 2 || l2 < 2 || d <= 0 || dyadic < 0 || dyadic > 8 || (solver != 0 && solver != 1))
+    return GPSIG_EINVAL;
+  if (pair_mode != GPSIG_PAIRS_RECT && pair_mode != GPSIG_PAIRS_UPPER && pair_mode != GPSIG_PAIRS_DIAG)
+    return GPSIG_EINVAL;
+  for (int i = 0; i < GPSIG_PDE_ROUTE_INTS; ++i) out[i] = 0;
+  if (!adjoint) return pde_fwd_route(l1, l2, d, dyadic, solver, pair_mode, out);
+  if (pair_mode == GPSIG_PAIRS_UPPER) return GPSIG_EINVAL;  // the adjoint has no UPPER mode
+  const PdeLayout lay = pde_layout_eff(l1, l2, dyadic);
+  if (lay.pair_floats == 0) return GPSIG_EUNSUPPORTED;
+  const bool tiled = pde_bwd_tiled(d, dyadic);
+  const int sub = tiled ? pde_bwd_sub(dyadic) : 0;
+  out[0] = tiled;
+  out[1] = tiled ? 0 : pde_dp(d);
+  out[2] = 1 << (dyadic - sub);
+  out[3] = lay.W;
+  out[4] = lay.H;
+  out[5] = lay.nblk;
+  out[6] = sub;
+  out[7] = pde_adj_wpb(l1, l2, d, dyadic, pair_mode, 0);
+  out[8] = pde_adj_wpb(l1, l2, d, dyadic, pair_mode, 1);
+  return GPSIG_OK;
+}
+
 // The tiled adjoint: per chunk of x-rows the increment tile (GEMM), the kernel (fronts / adjoint sums into
 // the adjoint tile), and the contractions dLoss/d dx = G dY, dLoss/d dy = G^T dX (GEMMs); point gradients at
 // the end.  a: filled by pde_adj_impl (mode fields, rows, fronts of the whole call).
@@ -98,7 +136,7 @@ static int pde_adj_tiled(PdeBwdArgs a, int mode, void *scratch, size_t scratch_b
   a.sub = pde_bwd_sub(a.dyadic);
   a.inc = Tin;
   a.gt = Tg;
-  a.wpb = 4;  // no per-wave LDS on tiles
+  a.wpb = pde_adj_wpb(l1, l2, d, a.dyadic, pm, mode);  // 4: no per-wave LDS on tiles
   const long long pf = pde_front_floats(l1, l2, a.dyadic);
   const int rb0 = a.row_begin, rb1 = a.row_end;
   for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += pl.rows) {
@@ -187,12 +225,8 @@ static int pde_adj_impl(int mode, const float *X, int n1, int l1, const float *Y
   a.fronts = static_cast<float *>(workspace);
   a.out = out;
   if (pde_bwd_tiled(d, dyadic)) return pde_adj_tiled(a, mode, scratch, scratch_bytes, s);
-  // pairs per workgroup: 4 unless the per-wave LDS (row accumulators and dx of x) of long x needs fewer
-  const int dp = d <= 8 ? d : (d <= 16 ? 16 : 0);
-  int wpb = 4;
-  // cross pairs also keep their lanes' column sums in LDS (W / REP coarse columns per lane)
-  const int wc = pair_mode == GPSIG_PAIRS_RECT && mode != 1 ? pde_layout(l1, l2, dyadic).W >> dyadic : 0;
-  while (wpb > 1 && (size_t)wpb * pde_lds_wave_doubles(l1 - 1, dp, wc) * sizeof(double) > 160 * 1024) wpb /= 2;
+  const int dp = pde_dp(d);
+  const int wpb = pde_adj_wpb(l1, l2, d, dyadic, pair_mode, mode);
   a.wpb = wpb;
   // not pair_tiles: wpb (not 4) rows per workgroup, one y-sequence per tile, no UPPER mode
   long long nblocks;

@@ -379,6 +379,8 @@ def pde_gram_vjp(X: torch.Tensor, Y: torch.Tensor | None, gout: torch.Tensor, dy
         raise ValueError(f"gout must be {(n1, n2)}")
     gX = torch.zeros((n1, l1, d), dtype=torch.float32, device=X.device)
     gY = gX if sym else torch.zeros((n2, l2, d), dtype=torch.float32, device=X.device)
+    if n1 == 0 or n2 == 0:  # no pairs: zero gradients (as pde_gram's empty output)
+        return gX, (None if sym else gY)
     per = lib.gpsig_pde_vjp_workspace_bytes(n2, l1, l2, dyadic)
     step = max(4, (min(n1, PDE_VJP_SCRATCH // max(per, 1)) // 4) * 4)
     sp, sb = _sp(scratch(X.device, lib.gpsig_pde_vjp_scratch_bytes(n1, l1, n2, l2, d, dyadic, L.PAIRS_RECT)))
@@ -413,6 +415,8 @@ def pde_fronts(X: torch.Tensor, Y: torch.Tensor | None, dyadic: int, solver: int
     if fronts.dtype != torch.float32 or not fronts.is_contiguous() or fronts.numel() * 4 < pde_fronts_bytes(npairs, l1, l2, dyadic):
         raise ValueError("fronts must be a contiguous float32 buffer of pde_fronts_bytes() bytes")
     out = torch.empty((n1,) if diag else (n1, n2), dtype=torch.float32, device=X.device)
+    if npairs == 0:
+        return out
     pm = L.PAIRS_DIAG if diag else L.PAIRS_RECT
     sp, sb = _sp(scratch(X.device, lib.gpsig_pde_vjp_scratch_bytes(n1, l1, n2, l2, d, dyadic, pm)))
     rc = lib.gpsig_pde_fronts_ex(X.data_ptr(), n1, l1, Y.data_ptr(), n2, l2, d, dyadic, solver, pm, 0, n1,
@@ -436,6 +440,8 @@ def pde_vjp_fronts(X: torch.Tensor, Y: torch.Tensor | None, gout: torch.Tensor, 
     n2, l2, _ = Y.shape
     gX = torch.zeros((n1, l1, d), dtype=torch.float32, device=X.device)
     gY = gX if (sym or diag) else torch.zeros((n2, l2, d), dtype=torch.float32, device=X.device)
+    if n1 == 0 or n2 == 0:  # no pairs: zero gradients
+        return gX if diag else (gX, (None if sym else gY))
     pm = L.PAIRS_DIAG if diag else L.PAIRS_RECT
     sp, sb = _sp(scratch(X.device, lib.gpsig_pde_vjp_scratch_bytes(n1, l1, n2, l2, d, dyadic, pm)))
     rc = lib.gpsig_pde_vjp_fronts_ex(X.data_ptr(), n1, l1, Y.data_ptr(), n2, l2, d, dyadic, solver, pm, 0, n1,
@@ -445,6 +451,22 @@ def pde_vjp_fronts(X: torch.Tensor, Y: torch.Tensor | None, gout: torch.Tensor, 
     if diag:
         return gX
     return gX, (None if sym else gY)
+
+
+def pde_route(l1: int, l2: int, d: int, dyadic: int = 0, solver: int = 1, pair_mode: int = L.PAIRS_RECT,
+              adjoint: bool = False) -> dict:
+    """What the launch path would choose for a shape (gpsig_pde_route: host only, no launch, no device).
+    Forward: family ('pair', 'lane_group', 'tile'), DP, REP, W, LP, nblk, sub; adjoint: tiled, DP, REP, W, H,
+    nblk, sub, wpb (gpsig_pde_vjp / gpsig_pde_vjp_fronts), wpb_fronts (gpsig_pde_fronts)."""
+    import ctypes
+    out = (ctypes.c_int * 9)()
+    L.check(L.load().gpsig_pde_route(l1, l2, d, dyadic, solver, pair_mode, int(bool(adjoint)), out), "gpsig_pde_route")
+    if adjoint:
+        keys = ("tiled", "DP", "REP", "W", "H", "nblk", "sub", "wpb", "wpb_fronts")
+        return dict(zip(keys, out))
+    r = dict(zip(("family", "DP", "REP", "W", "LP", "nblk", "sub"), out))
+    r["family"] = ("pair", "lane_group", "tile")[r["family"]]
+    return r
 
 
 # ----------------------------------------------------------------------------- signature features

@@ -318,6 +318,22 @@ int gpsig_pde_vjp_fronts_ex(const float *X, int n1, int l1, const float *Y, int 
                             float *gY, const void *fronts, size_t fronts_bytes, void *scratch, size_t scratch_bytes,
                             gpsig_stream_t stream);
 
+/* Host-only route query: what the launch path of the entries above would choose for a shape, computed by the
+ * helpers the launch path itself calls; launches nothing and touches no device.  out: GPSIG_PDE_ROUTE_INTS
+ * ints.  adjoint = 0 (gpsig_pde_gram_ex / gpsig_pde_diag_ex):
+ *   out[0] family: 0 one pair per wave, 1 lane groups (64 / LP pairs per wave), 2 one pair per wave on
+ *          increment tiles (lane groups never run on tiles)
+ *   out[1] DP (channel instantiation: d for d <= 8, 16 for d = 9..16, 0 on tiles)   out[2] the kernel's REP
+ *   out[3] W   out[4] LP (64: one pair per wave)   out[5] column blocks   out[6] sub (tile cells split 2^sub)
+ * adjoint = 1 (gpsig_pde_vjp_ex / gpsig_pde_fronts_ex / gpsig_pde_vjp_fronts_ex; pair_mode RECT or DIAG):
+ *   out[0] 0 fixed-channel kernels, 1 increment tiles   out[1] DP   out[2] REP   out[3] W
+ *   out[4] H (coarse steps per stored front)   out[5] column blocks   out[6] sub
+ *   out[7] pairs per workgroup (wpb) of gpsig_pde_vjp and gpsig_pde_vjp_fronts   out[8] wpb of gpsig_pde_fronts
+ * Returns GPSIG_OK, GPSIG_EINVAL, or GPSIG_EUNSUPPORTED for a grid no layout covers (the adjoint past 2^24 split
+ * cells per side; a launch can still refuse a covered shape whose x does not fit the LDS). */
+#define GPSIG_PDE_ROUTE_INTS 9
+int gpsig_pde_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode, int adjoint, int *out);
+
 /* ---------------------------------------------------------------------------------------------
  * Truncated signatures (replaces iisignature.sig behind iisignature_tensorflow.Sig,
  * gpsig/iisignature_tensorflow.py:87, used by the VOSF Kuf, gpsig/inducing_variables_vosf.py:120-146).

@@ -18,7 +18,8 @@ def header_symbols():
 
 def test_header_declares_expected_entry_points():
     syms = header_symbols()
-    for s in ["gpsig_sig_gram", "gpsig_sig_diag", "gpsig_pde_gram", "gpsig_pde_diag", "gpsig_tens_vs_seq",
+    for s in ["gpsig_sig_gram", "gpsig_sig_diag", "gpsig_pde_gram", "gpsig_pde_diag", "gpsig_pde_route",
+              "gpsig_tens_vs_seq",
               "gpsig_tens_gram", "gpsig_rescaled", "gpsig_sym_assemble", "gpsig_version"]:
         assert s in syms, s
 
@@ -106,6 +107,41 @@ def test_vjp_and_feature_entry_points_validate_arguments():
     assert lib.gpsig_pde_vjp_workspace_bytes(2, 10, 10, 4) == lib.gpsig_pde_vjp_workspace_bytes(2, 19, 19, 3)
     assert lib.gpsig_pde_vjp_workspace_bytes(2, 10, 10, 7) == lib.gpsig_pde_vjp_workspace_bytes(2, 145, 145, 3)
     assert lib.gpsig_pde_vjp_workspace_bytes(2, 10, 10, 9) == 0
+
+
+@pytest.mark.skipif("GPSIG_PDE_LP" in os.environ, reason="GPSIG_PDE_LP pins the lane group the query reports")
+def test_pde_route_query_without_gpu():
+    """gpsig_pde_route is host only: the launch path's choices for a shape, no device touched."""
+    import gpsig_amd._lib as L
+    from gpsig_amd import ops
+    lib = L.load()
+    out = (ctypes.c_int * 9)()
+    assert lib.gpsig_pde_route(1, 9, 3, 0, 1, 0, 0, out) == L.GPSIG_EINVAL       # l1 < 2
+    assert lib.gpsig_pde_route(9, 9, 3, 9, 1, 0, 0, out) == L.GPSIG_EINVAL       # dyadic > 8
+    assert lib.gpsig_pde_route(9, 9, 3, 0, 1, 1, 1, out) == L.GPSIG_EINVAL       # the adjoint has no UPPER mode
+    assert lib.gpsig_pde_route(9, 9, 3, 0, 1, 0, 0, None) == L.GPSIG_EINVAL
+    # solver-1 Gram pairs, d <= 8: lane groups; 128 columns fill (16, 8), one more goes to (16, 14)
+    assert ops.pde_route(9, 129, 3, 0, 1, L.PAIRS_RECT) == dict(family="lane_group", DP=3, REP=1, W=8, LP=16, nblk=1, sub=0)
+    assert ops.pde_route(9, 130, 3, 0, 1, L.PAIRS_RECT)["W"] == 14
+    # k(x, x), solver 0, d > 8: one pair per wave; W = 3 REP at 129 .. 192 coarse columns, blocks past 256
+    assert ops.pde_route(9, 194, 3, 1, 1, L.PAIRS_DIAG) == dict(family="pair", DP=3, REP=2, W=8, LP=64, nblk=1, sub=0)
+    assert ops.pde_route(9, 193, 12, 1, 0, L.PAIRS_RECT) == dict(family="pair", DP=16, REP=2, W=6, LP=64, nblk=1, sub=0)
+    assert ops.pde_route(9, 258, 12, 2, 1, L.PAIRS_RECT)["nblk"] == 2
+    assert ops.pde_route(9, 66, 5, 3, 1, L.PAIRS_RECT) == dict(family="pair", DP=5, REP=8, W=16, LP=64, nblk=1, sub=0)
+    # increment tiles: d > 16, or dyadic > 4 with the tile cells split 2^sub ways
+    assert ops.pde_route(9, 9, 17, 0, 1, L.PAIRS_UPPER) == dict(family="tile", DP=0, REP=1, W=1, LP=64, nblk=1, sub=0)
+    assert ops.pde_route(9, 9, 3, 6, 1, L.PAIRS_RECT) == dict(family="tile", DP=0, REP=16, W=16, LP=64, nblk=1, sub=2)
+    # adjoint: W, H, blocks as gpsig_pde_vjp_workspace_bytes' layouts above; tiles past d = 16 and dyadic 3
+    assert ops.pde_route(10, 10, 3, 1, 1, L.PAIRS_RECT, True) == dict(tiled=0, DP=3, REP=2, W=2, H=8, nblk=1, sub=0, wpb=4,
+                                                                      wpb_fronts=4)
+    assert ops.pde_route(10, 1100, 3, 0, 1, L.PAIRS_DIAG, True) == dict(tiled=0, DP=3, REP=1, W=16, H=2, nblk=2, sub=0,
+                                                                        wpb=4, wpb_fronts=4)
+    assert ops.pde_route(10, 10, 3, 4, 1, L.PAIRS_RECT, True) == dict(tiled=1, DP=0, REP=8, W=8, H=1, nblk=1, sub=1, wpb=4,
+                                                                      wpb_fronts=4)
+    # long x at DP 16: the per-wave LDS leaves 2 pairs, then 1 pair per workgroup
+    assert ops.pde_route(200, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb"] == 2
+    assert ops.pde_route(200, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb_fronts"] == 4
+    assert ops.pde_route(450, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb"] == 1
 
 
 def test_graph_capture_refuses_host_tensors_and_kernel_to():

@@ -25,6 +25,37 @@ def test_kdiag_grad_oracle_pinned_and_consistent(n, solver):
             np.testing.assert_allclose(gx + gy, ref[a], rtol=1e-9, atol=1e-11)
 
 
+@pytest.mark.parametrize("d", [1, 3, 9])
+@pytest.mark.parametrize("solver", [0, 1])
+@pytest.mark.parametrize("n", [0, 1, 2])
+def test_c_adjoint_oracle_pinned_to_restatement(n, solver, d):
+    """pde.pde_gram_grad (the C adjoint the GPU tests lean on) against the NumPy restatement that is pinned to the
+    reference's own grids above: cross pairs of unequal lengths by pair_grad, and x-part + y-part of the pair
+    (x, x) by kdiag_grad on the C grids; fp64 round-off only."""
+    rng = np.random.default_rng(100 * n + 10 * solver + d)
+    X = np.cumsum(rng.standard_normal((3, 7, d)), 1) * 0.3
+    Y = np.cumsum(rng.standard_normal((2, 5, d)), 1) * 0.3
+    G = rng.standard_normal((3, 2))
+    gX, gY = pde.pde_gram_grad(X, Y, G, n, solver)
+    rx, ry = np.zeros_like(X), np.zeros_like(Y)
+    for a in range(3):
+        for b in range(2):
+            gx, gy = pde_grad.pair_grad(X[a], Y[b], n, solver)
+            rx[a] += G[a, b] * gx
+            ry[b] += G[a, b] * gy
+    assert np.abs(rx).max() > 1e-3 and np.abs(ry).max() > 1e-3
+    np.testing.assert_allclose(gX, rx, rtol=1e-12, atol=1e-10)
+    np.testing.assert_allclose(gY, ry, rtol=1e-12, atol=1e-10)
+    # k(x, x): the diagonal formula on the restated grids.  With solver 0 the reference's diagonal cells take the
+    # second-order update (sigKer_fast.pyx:59), which the cross-pair scheme of pde_gram_grad does not: solver 1 only
+    if solver == 1:
+        K, Kr = pde.pde_diag_grids(X, n, solver)
+        ref = pde_grad.kdiag_grad(X, np.tril(K), np.tril(Kr), n)
+        for a in range(3):
+            gx, gy = pde.pde_gram_grad(X[a:a + 1], X[a:a + 1], np.ones((1, 1)), n, solver)
+            np.testing.assert_allclose(gx[0] + gy[0], ref[a], rtol=1e-9, atol=1e-11)
+
+
 def test_pair_grad_approximates_derivative():
     """The adjoint is the continuous-PDE derivative (K_rev by the first-order scheme): it approximates
     finite differences of the discrete solve up to the discretisation error (a few % at dyadic 2)."""
