@@ -89,6 +89,7 @@ SIGNATURES = {
     "gpsig_tens_gram_vjp": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "gpsig_rescaled": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "gpsig_rescaled_workspace_bytes": (_SZ, [_I, _I]),
+    "gpsig_rescaled_vjp": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "gpsig_tens_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "gpsig_signature_channels": (ctypes.c_longlong, [_I, _I]),
     "gpsig_signature": (_I, [_P, _I, _I, _I, _I, _P, _P]),

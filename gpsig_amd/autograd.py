@@ -537,6 +537,24 @@ class TensGram(torch.autograd.Function):
         return gZ.to(Zs.dtype), None
 
 
+class Rescaled(torch.autograd.Function):
+    """Raw per-level VOSF rescaled kernel (ops.rescaled, the variance term of Mahalanobis_term_approx_posterior)
+    with a gfx950 backward (gpsig_rescaled_vjp) for dLoss/dZ and dLoss/dX."""
+
+    @staticmethod
+    def forward(ctx, Zs, Xs, num_levels, embedding):
+        ctx.num_levels, ctx.embedding = num_levels, embedding
+        ctx.save_for_backward(Zs, Xs)
+        return ops.rescaled(Zs.detach(), Xs.detach(), num_levels, embedding=embedding)
+
+    @staticmethod
+    def backward(ctx, gout):
+        Zs, Xs = ctx.saved_tensors
+        gZ, gX = ops.rescaled_vjp(Zs.detach(), Xs.detach(), ctx.num_levels, gout, embedding=ctx.embedding)
+        return (gZ.to(Zs.dtype) if ctx.needs_input_grad[0] else None,
+                gX.to(Xs.dtype) if ctx.needs_input_grad[1] else None, None, None)
+
+
 PDE_FRONTS_BYTES = int(os.environ.get("GPSIG_PDE_FRONTS_BYTES", 16 << 30))
 
 

@@ -503,7 +503,7 @@ class SignatureKernel:
     # ------------------------------------------------------------------ VOSF helpers (kernels.py:800-940)
     def _Mahalanobis_term_approx_posterior(self, Z, X):
         """kernels.py:800-822 (linear embedding): (num_levels+1, N, T)."""
-        return ops.rescaled(Z, X, self.num_levels, embedding="linear")
+        return _ag.Rescaled.apply(Z, X, self.num_levels, "linear")
 
     def Mahalanobis_term_approx_posterior(self, Z, X, presliced=False):
         """kernels.py:876-895."""

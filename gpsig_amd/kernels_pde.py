@@ -155,7 +155,7 @@ class UntruncSignatureKernel:
         """kernels_pde.py:310-330 (per-coordinate RBF embedding, rescaled higher-order recursion)."""
         Zt = _as_tensor(Z)
         Xs = self._prep(X)
-        K = ops.rescaled(Zt[1:], Xs, self.num_levels, embedding=self._embedding()) * float(self.sigma)
+        K = _ag.Rescaled.apply(Zt[1:], Xs, self.num_levels, self._embedding()) * float(self.sigma)
         return (K.sum(0) + 1.0 - Zt[0, :, 0].to(K)[None, :]).to(self._dt(X))
 
     def Mahalanobis_tens(self, Z, beta):

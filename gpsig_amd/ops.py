@@ -694,3 +694,29 @@ def rescaled(Z: torch.Tensor, X: torch.Tensor, num_levels: int, embedding: str =
                             out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(X.device))
     L.check(rc, "gpsig_rescaled")
     return out
+
+
+def rescaled_vjp(Z: torch.Tensor, X: torch.Tensor, num_levels: int, gout: torch.Tensor,
+                 embedding: str = "linear") -> tuple[torch.Tensor, torch.Tensor]:
+    """(dLoss/dZ, dLoss/dX) of `rescaled` given gout (M+1, N, T) (gpsig_rescaled_vjp); level 0 of gout is ignored."""
+    _require_cuda(Z, X, gout)
+    lt, t, d = Z.shape
+    n, l, dx = X.shape
+    if dx != d:
+        raise ValueError("Z and X must have the same channel count")
+    if lt != num_levels * (num_levels + 1) // 2:
+        raise ValueError(f"Z must have num_levels*(num_levels+1)/2 = {num_levels * (num_levels + 1) // 2} components")
+    if tuple(gout.shape) != (num_levels + 1, n, t):
+        raise ValueError(f"gout must be (num_levels+1, N, T) = {(num_levels + 1, n, t)}")
+    lib = L.load()
+    Z, X, gout = _f32(Z), _f32(X), _f32(gout)
+    gZ = torch.zeros(Z.shape, dtype=torch.float32, device=X.device)
+    gX = torch.zeros(X.shape, dtype=torch.float32, device=X.device)
+    if n == 0:
+        return gZ, gX
+    ws = workspace(X.device, lib.gpsig_rescaled_workspace_bytes(n, num_levels))
+    rc = lib.gpsig_rescaled_vjp(Z.data_ptr(), lt, t, X.data_ptr(), n, l, d, num_levels, EMBEDDINGS[embedding],
+                                gout.data_ptr(), gZ.data_ptr(), gX.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _stream(X.device))
+    L.check(rc, "gpsig_rescaled_vjp")
+    return gZ, gX

@@ -242,6 +242,18 @@ size_t gpsig_rescaled_workspace_bytes(int n, int num_levels);
 int gpsig_rescaled(const float *Z, int lt, int t, const float *X, int n, int l, int d, int num_levels,
                    int embedding, float *out, void *workspace, size_t workspace_bytes, gpsig_stream_t stream);
 
+/* Gradient of gpsig_rescaled by Z and X (the reference differentiates _Mahalanobis_term_approx_posterior +
+ * signature_kern_rescaled_higher_order, signature_algs_vosf.py:11-48, by TF autodiff and keeps the
+ * (N, L, LT, 2T, L) tensors; here nothing of size N T L^2 touches memory).  gout (num_levels+1, n, T) =
+ * dLoss/d(out), level 0 ignored; accumulates (+=) gZ (LT, T, d) and gX (n, l, d).  Stream-ordered, allocates
+ * nothing.  The envelope is the forward's: num_levels <= 6, l - 1 <= 128, or l - 1 <= 256 up to num_levels = 4,
+ * both embeddings, any d; GPSIG_EUNSUPPORTED outside it with nothing launched, GPSIG_EINVAL for null
+ * pointers and bad shapes.  Workspace as gpsig_rescaled: gpsig_rescaled_workspace_bytes(n, num_levels) bytes (the
+ * weights of the ones tensor, one float per sequence and level); GPSIG_EWORKSPACE below that. */
+int gpsig_rescaled_vjp(const float *Z, int lt, int t, const float *X, int n, int l, int d, int num_levels,
+                       int embedding, const float *gout, float *gZ, float *gX, void *workspace,
+                       size_t workspace_bytes, gpsig_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Goursat PDE (untruncated signature kernel).
  *

@@ -4,7 +4,7 @@ device-synchronised calls, inputs resident), with the gradient's error vs torch 
 reference graph (oracle/autodiff_ref.py) / the reference's PDE adjoint (oracle/pde_grad.py) on a
 subsample.  One JSON object per line.
 
-    python tools/bench_grad.py [--only gram,kuf,kuf_incr,pde,pde_gram,sig,svgp46,svgp126]
+    python tools/bench_grad.py [--only gram,kuf,kuf_incr,pde,pde_gram,sig,svgp46,svgp126,vosf_kdiag,rescaled_linear,rescaled_rbf]
 """
 import argparse
 import json
@@ -287,6 +287,41 @@ def bench_vosf_kdiag(reps, n=50, l=500, nf=23, m=5):
                 fwd_ms=tf * 1e3, fwd_bwd_ms=tb * 1e3, grad_err=rel(Xs.grad.reshape(Xr.shape).cpu().numpy(), Xr.grad.numpy()))
 
 
+def bench_rescaled(reps, embedding, n=256, t=64, l=64, d=5, m=4):
+    """The VOSF variance term's raw kernel (ops.rescaled, the shape of tools/bench_tvs_generic.py) forward and
+    backward to Z and X (gpsig_rescaled_vjp); the error against fp64 autodiff of the reference graph
+    (tests/rescaled_autodiff.py) on two sequences and two tensors."""
+    from gpsig_amd import autograd as ag
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rescaled_autodiff as ra
+    rng = np.random.default_rng(0)
+    Xnp = np.cumsum(rng.standard_normal((n, l, d)), 1) / np.sqrt(l)
+    Znp = rng.uniform(0.1, 0.9, (m * (m + 1) // 2, t, d))
+    X = torch.tensor(Xnp, device="cuda", dtype=torch.float32)
+    Z = torch.tensor(Znp, device="cuda", dtype=torch.float32)
+    G = torch.randn(m + 1, n, t, device="cuda")
+
+    def fwd():
+        with torch.no_grad():
+            ag.Rescaled.apply(Z, X, m, embedding)
+
+    def fb():
+        Zg, Xg = Z.detach().requires_grad_(True), X.detach().requires_grad_(True)
+        (ag.Rescaled.apply(Zg, Xg, m, embedding) * G).sum().backward()
+
+    tf, tb = timed(fwd, reps), timed(fb, reps)
+    S, TS = 2, 2
+    Zs = torch.tensor(Znp[:, :TS], device="cuda", dtype=torch.float32, requires_grad=True)
+    Xs = torch.tensor(Xnp[:S], device="cuda", dtype=torch.float32, requires_grad=True)
+    Gs = rng.standard_normal((m + 1, S, TS))
+    (ag.Rescaled.apply(Zs, Xs, m, embedding) * torch.tensor(Gs, device="cuda", dtype=torch.float32)).sum().backward()
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)
+    rZ, rX = ra.grads(embedding, f32(Znp[:, :TS]), f32(Xnp[:S]), m, f32(Gs))
+    err = max(rel(Zs.grad.cpu().numpy(), rZ), rel(Xs.grad.cpu().numpy(), rX))
+    return dict(path=f"rescaled_{embedding}", workload=f"ops.rescaled {embedding} N={n} T={t} L={l} D={d} M={m} (dZ, dX)",
+                fwd_ms=tf * 1e3, fwd_bwd_ms=tb * 1e3, grad_err=err)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -297,7 +332,9 @@ def main():
                 kuf_incr=lambda: bench_kuf(a.reps, increments=True), pde=lambda: bench_pde(a.reps),
                 pde_gram=lambda: bench_pde_gram(a.reps),
                 sig=lambda: bench_sig(a.reps), svgp46=lambda: bench_svgp(a.reps, nf=23),
-                svgp126=lambda: bench_svgp(a.reps, nf=63), vosf_kdiag=lambda: bench_vosf_kdiag(a.reps))
+                svgp126=lambda: bench_svgp(a.reps, nf=63), vosf_kdiag=lambda: bench_vosf_kdiag(a.reps),
+                rescaled_linear=lambda: bench_rescaled(a.reps, "linear"),
+                rescaled_rbf=lambda: bench_rescaled(a.reps, "rbf"))
     for name in todo:
         r = runs[name]()
         r["bwd_over_fwd"] = (r["fwd_bwd_ms"] - r["fwd_ms"]) / r["fwd_ms"]
