@@ -242,6 +242,44 @@ static int sig_gram_impl(const float *X, int n1, int l1, const float *Y, int n2,
   return (order == 1) ? sig_fo_launch(a, DP, seed, t.nblocks, s) : sig_ho_launch(a, DP, seed, t.nblocks, s);
 }
 
+// gpsig_sig_ho_route: the choices of sig_gram_impl at order > 1 and of sig_ho_launch / sig_ho_tiled under it,
+// in sig_gram_impl's order and by the helpers it calls (ho_tiled, gram_plan, ho_lanes_per_pair, pair_tiles;
+// sig_ho.hip: ho_w, ho_plan, the tile chunks); no launch, no device
+extern "C" int gpsig_sig_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
+                                  int difference, int pair_mode, int row_begin, int row_end, int *out) {
+  if (!out || num_levels < 1 || order < 2) return GPSIG_EINVAL;
+  // the query has no inputs: out stands in for the pointers the shared check wants present
+  if (check_pair_args(out, out, n1, l1, n2, l2, d, difference ? 2 : 1, pair_mode, row_begin, row_end, false))
+    return GPSIG_EINVAL;
+  for (int i = 0; i < GPSIG_SIG_HO_ROUTE_INTS; ++i) out[i] = 0;
+  if (base_kind & (GPSIG_BASE_SEED_MFMA | GPSIG_GRAM_SPLIT)) return GPSIG_EUNSUPPORTED;  // first-order variants
+  const int seed = seed_of(base_kind, difference);
+  const bool tiled = ho_tiled(d, order);
+  if (tiled && seed != SEED_LIN_DIFF && seed != SEED_RBF_DIFF) return GPSIG_EUNSUPPORTED;
+  GramPlan pl{};
+  const bool planned = !tiled && gram_plan(n1, l1, n2, l2, d, num_levels, order, seed, pair_mode,
+                                           pair_mode != GPSIG_PAIRS_RECT, false, false, &pl);
+  if (seed < 0 || (!planned && !tiled)) return GPSIG_EUNSUPPORTED;
+  HoRoute r{};
+  int rc;
+  if (tiled) {
+    rc = sig_ho_tiled_route(n1, l1, n2, l2, d, num_levels, order, seed, pair_mode, row_begin, row_end, &r);
+  } else {
+    if (ho_lanes_per_pair(l2, order, num_levels) == 0) return GPSIG_EUNSUPPORTED;
+    PairTiles t{};
+    if (row_end > row_begin && (rc = pair_tiles(pair_mode, row_begin, row_end, n2, 1, &t))) return rc;
+    rc = sig_ho_route(l1, l2, num_levels, order, seed, t.nblocks, &r);
+  }
+  out[0] = tiled ? 1 : 0;
+  out[1] = tiled ? 0 : pl.DP;
+  out[2] = r.W;
+  out[3] = r.nblk;
+  out[4] = r.split;
+  out[5] = r.carry > 0x7fffffff ? 0x7fffffff : (int)r.carry;
+  out[6] = r.launches;
+  return row_end == row_begin ? GPSIG_OK : rc;  // no rows: the entry returns before any launch
+}
+
 extern "C" int gpsig_sig_gram(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int num_levels,
                               int order, int base_kind, int difference, int pair_mode, int row_begin, int row_end,
                               const float *rs1, const float *rs2, const float *scale, float jitter, int out_mode,

@@ -43,6 +43,14 @@ bool ho_tiled(int d, int order);
 size_t ho_tile_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode);
 int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, void *workspace, size_t workspace_bytes,
                  hipStream_t s);
+// gpsig_sig_ho_route: what sig_ho_launch (nblocks workgroups) / sig_ho_tiled would choose, and their return
+struct HoRoute {
+  int W, nblk, split, launches;  // columns per lane, column blocks, SPLIT kernel, kernel launches (tile mode: chunks)
+  size_t carry;                  // dynamic LDS of the plain blocked kernel's carries
+};
+int sig_ho_route(int l1, int l2, int M, int order, int seed, long long nblocks, HoRoute *r);
+int sig_ho_tiled_route(int n1, int l1, int n2, int l2, int d, int M, int order, int seed, int pair_mode,
+                       int row_begin, int row_end, HoRoute *r);
 
 // ---- pde.hip: the Goursat PDE forward and the increment tiles
 int pde_launch(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int dyadic, int solver,

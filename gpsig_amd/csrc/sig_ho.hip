@@ -386,23 +386,63 @@ constexpr size_t HO_MAX_CARRY_BYTES = 160 * 1024;
 // two waves per SIMD the plain kernel leaves the chip idle (GPSIG_HO_SPLIT=0 keeps the plain kernel: host.h)
 constexpr long long HO_SPLIT_PAIRS = 2048;
 
+// The kernel form of one launch of nblocks 4-pair workgroups at W columns per lane (launch_ho and the route query
+// decide by this): the column blocks, SPLIT or plain, the plain kernel's carry LDS.  GPSIG_EUNSUPPORTED when
+// the carries of the plain kernel do not fit the LDS.
+struct HoPlan {
+  int nblk;
+  bool split;
+  size_t lds;
+};
+static int ho_plan(int l1, int l2, int W, int order, int M, long long nblocks, HoPlan *p) {
+  p->nblk = ho_blocks(l2, W);
+  p->split = p->nblk >= 2 && p->nblk <= 4 && nblocks * 4 <= HO_SPLIT_PAIRS && ho_split_on();
+  p->lds = p->split ? 0 : ho_carry_bytes(l1, order, M, p->nblk);
+  return p->lds > HO_MAX_CARRY_BYTES ? GPSIG_EUNSUPPORTED : GPSIG_OK;
+}
+
 template <int DP, int W, int ORD, int SEED, bool TILE = false>
 static int launch_ho(const SigArgs &a0, long long nblocks, hipStream_t s) {
   if (nblocks <= 0) return GPSIG_OK;
   SigArgs a = a0;
-  a.nblk = ho_blocks(a.l2, W);
-  if (a.nblk >= 2 && a.nblk <= 4 && nblocks * 4 <= HO_SPLIT_PAIRS && ho_split_on()) {
+  HoPlan pl;
+  if (const int rc = ho_plan(a.l1, a.l2, W, ORD, a.M, nblocks, &pl)) return rc;
+  a.nblk = pl.nblk;
+  if (pl.split) {
     hipLaunchKernelGGL((sig_ho_kernel<DP, W, ORD, 8, SEED, TILE, true>), dim3((unsigned)(nblocks * 4)), dim3(256), 0,
                        s, a);
     return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
   }
-  const size_t lds = ho_carry_bytes(a.l1, ORD, a.M, a.nblk);
-  if (lds > HO_MAX_CARRY_BYTES) return GPSIG_EUNSUPPORTED;
-  hipLaunchKernelGGL((sig_ho_kernel<DP, W, ORD, 8, SEED, TILE>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((sig_ho_kernel<DP, W, ORD, 8, SEED, TILE>), dim3((unsigned)nblocks), dim3(256), pl.lds, s, a);
   return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
 
 int ho_lanes_per_pair(int l2, int order, int M) { return (M <= 8 && order <= 8 && l2 >= 2) ? 64 : 0; }
+
+// the seeds and sizes the fixed-channel launch has instantiations for
+static int ho_launch_ok(int M, int order, int seed) {
+  if (!seed_is_diff(seed)) return GPSIG_EUNSUPPORTED;
+  if (M > 8 || order > 8 || order < 2) return GPSIG_EUNSUPPORTED;
+  return GPSIG_OK;
+}
+
+// gpsig_sig_ho_route, one launch: the W of ho_dispatch and the plan of launch_ho (no launch where nblocks <= 0)
+static int ho_route_launch(int l1, int l2, int M, int order, long long nblocks, HoRoute *r) {
+  r->W = ho_w(l2, order);
+  HoPlan pl;
+  const int rc = ho_plan(l1, l2, r->W, order, M, nblocks, &pl);
+  r->nblk = pl.nblk;
+  r->split = pl.split ? 1 : 0;
+  r->carry = pl.lds;
+  return nblocks > 0 ? rc : GPSIG_OK;
+}
+
+int sig_ho_route(int l1, int l2, int M, int order, int seed, long long nblocks, HoRoute *r) {
+  *r = HoRoute{};
+  if (const int rc = ho_launch_ok(M, order, seed)) return rc;
+  r->launches = nblocks > 0 ? 1 : 0;
+  return ho_route_launch(l1, l2, M, order, nblocks, r);
+}
 
 template <int DP, int SEED, bool TILE = false>
 static int ho_dispatch(const SigArgs &a, long long nblocks, hipStream_t s) {
@@ -421,8 +461,7 @@ static int ho_dispatch(const SigArgs &a, long long nblocks, hipStream_t s) {
 }
 
 int sig_ho_launch(const SigArgs &a, int DP, int seed, long long nblocks, hipStream_t s) {
-  if (!seed_is_diff(seed)) return GPSIG_EUNSUPPORTED;
-  if (a.M > 8 || a.order > 8 || a.order < 2) return GPSIG_EUNSUPPORTED;
+  if (const int rc = ho_launch_ok(a.M, a.order, seed)) return rc;
   return dispatch<4, 8, 16, 32>(DP, [&](auto dp) {
     constexpr int D = decltype(dp)::value;
     if (seed == SEED_RAD_DIFF) return ho_dispatch<D, SEED_RAD_DIFF>(a, nblocks, s);
@@ -448,6 +487,27 @@ size_t ho_tile_bytes(int n1, int l1, int n2, int l2, int d, int pair_mode) {
   return ho_operand_bytes(n1, l1, n2, l2, d, pair_mode) + align256((size_t)rows * (l1 - 1) * cols * sizeof(float));
 }
 
+// what the tile mode has kernels for: the linear increments, or the RBF cells of the matrix-core wide seed
+static int ho_tiled_ok(int M, int order, int d, int l2, int seed) {
+  if (M > 8 || order > 8) return GPSIG_EUNSUPPORTED;
+  if (seed == SEED_RBF_DIFF ? !mf_gram_applies(d, l2) : seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
+  return GPSIG_OK;
+}
+// The chunks of x-rows of a tiled call over rows [rb0, rb1): f(r0, r1, c0, pt, trc) with the chunk's tile rows
+// [r0, r1) (r0 a multiple of 4), its first evaluated row c0, and its workgroups pt (trc: pair_tiles' return);
+// stops at the first non-zero return.  One pair per wave: b-tiles are single sequences (G = 1).
+template <class F>
+static int ho_tile_chunks(int pm, int rb0, int rb1, int n2, int rows, F &&f) {
+  for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += rows) {
+    const int r1 = r0 + rows < rb1 ? r0 + rows : rb1;
+    const int c0 = r0 > rb0 ? r0 : rb0;
+    PairTiles pt;
+    const int trc = pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, 1, &pt);
+    if (const int rc = f(r0, r1, c0, pt, trc)) return rc;
+  }
+  return GPSIG_OK;
+}
+
 // Chunks of x-rows: the cell tile of the chunk -- linear: the increment Gram (one matrix-core GEMM dX_chunk dY^T,
 // batched per pair for DIAG); RBF: the difference-seed cells from the matrix-core wide seed (sig_fo_mf.h, cell
 // producer) -- then the tile-fed recursion.  a: filled by the caller (rows, mode, output, M, order).
@@ -455,13 +515,12 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
                  hipStream_t s) {
   const int n1 = a.n1, l1 = a.l1, n2 = a.n2, l2 = a.l2, pm = a.pair_mode;
   const int IC = l1 - 1, JC = l2 - 1;
-  if (a.M > 8 || a.order > 8) return GPSIG_EUNSUPPORTED;
+  if (const int rc = ho_tiled_ok(a.M, a.order, d, l2, seed)) return rc;
   if (!workspace || workspace_bytes < ho_tile_bytes(n1, l1, n2, l2, d, pm)) return GPSIG_EWORKSPACE;
   int rows;
   long long cols;
   pde_tile_chunk(n1, l1, n2, l2, pm, rows, cols);
   const bool rbf = seed == SEED_RBF_DIFF;
-  if (rbf ? !mf_gram_applies(d, l2) : seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
   char *w = static_cast<char *>(workspace);
   float *dX = reinterpret_cast<float *>(w), *dY = dX;
   const size_t xb = rbf ? align256(mf_records_bytes(n1, l1, d)) : align256((size_t)n1 * IC * d * sizeof(float));
@@ -476,16 +535,10 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
   a.RX = X;
   a.RY = pm == GPSIG_PAIRS_RECT ? Y : X;
   a.wd = d;
-  const int rb0 = a.row_begin, rb1 = a.row_end;
-  for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += rows) {
-    const int r1 = r0 + rows < rb1 ? r0 + rows : rb1;
-    const int c0 = r0 > rb0 ? r0 : rb0;
+  return ho_tile_chunks(pm, a.row_begin, a.row_end, n2, rows, [&](int r0, int r1, int c0, const PairTiles &pt, int trc) {
     SigArgs c = a;
     c.row_begin = c0;
     c.row_end = r1;
-    // one pair per wave: b-tiles are single sequences (G = 1)
-    PairTiles pt;
-    const int trc = pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, 1, &pt);
     c.tiles_a0 = pt.tiles_a0;
     c.ntb = pt.ntb;
     c.tile_base = pt.tile_base;
@@ -516,9 +569,36 @@ int sig_ho_tiled(SigArgs a, const float *X, const float *Y, int d, int seed, voi
     }
     if (rc) return rc;
     if (trc) return trc;
-    if ((rc = ho_dispatch<1, SEED_LIN_DIFF, true>(c, pt.nblocks, s))) return rc;
-  }
-  return GPSIG_OK;
+    return ho_dispatch<1, SEED_LIN_DIFF, true>(c, pt.nblocks, s);
+  });
+}
+
+// gpsig_sig_ho_route, tile mode: the chunks of sig_ho_tiled, each a launch planned as ho_dispatch -> launch_ho
+// does; W, blocks, split and carry bytes are the first chunk's (a shorter last chunk can have few enough pairs
+// for SPLIT where the others run plain), GPSIG_EUNSUPPORTED where some chunk's launch would return it
+int sig_ho_tiled_route(int n1, int l1, int n2, int l2, int d, int M, int order, int seed, int pair_mode,
+                       int row_begin, int row_end, HoRoute *r) {
+  *r = HoRoute{};
+  if (const int rc = ho_tiled_ok(M, order, d, l2, seed)) return rc;
+  int rows;
+  long long cols;
+  pde_tile_chunk(n1, l1, n2, l2, pair_mode, rows, cols);
+  HoRoute first{};
+  int launches = 0;
+  auto chunk = [&](int, int, int, const PairTiles &pt, int trc) {
+    if (trc) return trc;
+    HoRoute c{};
+    const int crc = ho_route_launch(l1, l2, M, order, pt.nblocks, &c);
+    if (launches == 0) first = c;
+    launches += pt.nblocks > 0 ? 1 : 0;
+    return crc;
+  };
+  // an empty row window never reaches sig_ho_tiled (whose first chunk starts at the multiple of 4 below it)
+  const int rc = row_end > row_begin ? ho_tile_chunks(pair_mode, row_begin, row_end, n2, rows, chunk) : GPSIG_OK;
+  if (launches == 0) ho_route_launch(l1, l2, M, order, 0, &first);  // no rows: the geometry alone
+  *r = first;
+  r->launches = launches;
+  return rc;
 }
 
 }  // namespace gpsig

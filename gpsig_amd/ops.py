@@ -222,6 +222,30 @@ def sig_gram(X: torch.Tensor, Y: torch.Tensor | None, num_levels: int, order: in
     return out
 
 
+def ho_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_levels: int, order: int, base="rbf",
+             difference: bool = True, diag: bool = False, rows: tuple | None = None) -> dict:
+    """What sig_gram / sig_diag at order >= 2 would run for a shape (gpsig_sig_ho_route: host only, no launch, no
+    device).  n2 None: the symmetric K(X) (diag=True: sig_diag).  tiled, DP, W, nblk (column blocks), split,
+    carry_bytes, launches as include/gpsig_amd.h describes them, and features: True where this module computes
+    the call from signature features (_sig_feature_path) and never reaches the recursion the other keys describe.
+    Raises GpsigError where the launch would (unsupported shapes: the carries past the LDS, difference=False)."""
+    import ctypes
+    sym = n2 is None
+    pm = L.PAIRS_DIAG if diag else (L.PAIRS_UPPER if sym else L.PAIRS_RECT)
+    if sym:
+        n2, l2 = n1, l1
+    r0, r1 = (0, n1) if rows is None else rows
+    out = (ctypes.c_int * 7)()
+    features = _sig_feature_path(order, base, difference, num_levels, d)
+    rc = L.load().gpsig_sig_ho_route(n1, l1, n2, l2, d, num_levels, order, base_kind(base), int(bool(difference)), pm,
+                                     r0, r1, out)
+    if not (features and rc == L.GPSIG_EUNSUPPORTED):  # the feature path takes what the recursion has no kernel for
+        L.check(rc, "gpsig_sig_ho_route")
+    r = dict(zip(("tiled", "DP", "W", "nblk", "split", "carry_bytes", "launches"), out))
+    r["features"] = features
+    return r
+
+
 def sig_state_numel(n1: int, n2: int | None, l2: int, num_levels: int) -> int:
     """float32 elements of the saved VJP state of a Gram call (n2 None: symmetric K(X), upper
     triangle)."""

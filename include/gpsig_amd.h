@@ -346,6 +346,22 @@ int gpsig_pde_vjp_fronts_ex(const float *X, int n1, int l1, const float *Y, int 
 #define GPSIG_PDE_ROUTE_INTS 9
 int gpsig_pde_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode, int adjoint, int *out);
 
+/* The same for the higher-order forward recursion (gpsig_sig_gram / gpsig_sig_diag at order >= 2), with the
+ * arguments that call decides by.  out: GPSIG_SIG_HO_ROUTE_INTS ints:
+ *   out[0] 1: cells from increment tiles (more than 32 channels), 0: fixed-channel feature records
+ *   out[1] DP (channel padding 4 / 8 / 16 / 32; 0 on tiles)   out[2] W (columns per lane: 1, 2, 4)
+ *   out[3] column blocks of 64 W - 1 cells   out[4] 1: the SPLIT kernel (one pair per workgroup, 2..4 blocks side
+ *          by side; few pairs, GPSIG_HO_SPLIT not 0), 0: one pair per wave
+ *   out[5] bytes of dynamic LDS for the carries of the one-pair-per-wave kernel's column blocks (0 otherwise)
+ *   out[6] kernel launches (row chunks on tiles; 0 for an empty row window)
+ * On tiles out[2..5] describe the first row chunk (a shorter last chunk can fall under the SPLIT bound on its
+ * own).  Returns GPSIG_OK; GPSIG_EINVAL for arguments the call rejects and for order < 2; GPSIG_EUNSUPPORTED
+ * where the call returns it: difference = 0, num_levels or order past 8, a base kernel without tile cells past
+ * 32 channels, and carries past 160 KiB (out is filled then, so out[5] shows the size). */
+#define GPSIG_SIG_HO_ROUTE_INTS 7
+int gpsig_sig_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
+                       int difference, int pair_mode, int row_begin, int row_end, int *out);
+
 /* ---------------------------------------------------------------------------------------------
  * Truncated signatures (replaces iisignature.sig behind iisignature_tensorflow.Sig,
  * gpsig/iisignature_tensorflow.py:87, used by the VOSF Kuf, gpsig/inducing_variables_vosf.py:120-146).

@@ -19,7 +19,7 @@ def header_symbols():
 def test_header_declares_expected_entry_points():
     syms = header_symbols()
     for s in ["gpsig_sig_gram", "gpsig_sig_diag", "gpsig_pde_gram", "gpsig_pde_diag", "gpsig_pde_route",
-              "gpsig_tens_vs_seq",
+              "gpsig_sig_ho_route", "gpsig_tens_vs_seq",
               "gpsig_tens_gram", "gpsig_rescaled", "gpsig_sym_assemble", "gpsig_version"]:
         assert s in syms, s
 
@@ -142,6 +142,63 @@ def test_pde_route_query_without_gpu():
     assert ops.pde_route(200, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb"] == 2
     assert ops.pde_route(200, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb_fronts"] == 4
     assert ops.pde_route(450, 7, 16, 0, 1, L.PAIRS_RECT, True)["wpb"] == 1
+
+
+@pytest.mark.skipif("GPSIG_HO_SPLIT" in os.environ, reason="GPSIG_HO_SPLIT pins the kernel form the query reports")
+def test_sig_ho_route_query_without_gpu(monkeypatch):
+    """gpsig_sig_ho_route is host only: what gpsig_sig_gram / gpsig_sig_diag at order >= 2 would run for a shape."""
+    import gpsig_amd
+    import gpsig_amd._lib as L
+    from gpsig_amd import ops
+    lib = L.load()
+    out = (ctypes.c_int * 7)()
+
+    def rc(n1=4, l1=45, n2=2, l2=40, d=3, M=4, order=3, base=L.BASE_RBF, diff=1, pm=L.PAIRS_RECT, r0=0, r1=4, o=out):
+        return lib.gpsig_sig_ho_route(n1, l1, n2, l2, d, M, order, base, diff, pm, r0, r1, o)
+    assert rc() == L.GPSIG_OK
+    assert rc(o=None) == L.GPSIG_EINVAL
+    assert rc(l2=1) == L.GPSIG_EINVAL                       # difference needs two points
+    assert rc(order=1) == L.GPSIG_EINVAL                    # the first-order kernels are not this query's
+    assert rc(r1=5) == L.GPSIG_EINVAL                       # row window past n1
+    assert rc(pm=L.PAIRS_UPPER) == L.GPSIG_EINVAL           # UPPER pairs X with itself: equal shapes
+    assert rc(pm=3) == L.GPSIG_EINVAL
+    assert rc(diff=0) == L.GPSIG_EUNSUPPORTED               # the higher-order seeds are the difference seeds
+    assert rc(M=9, order=9) == L.GPSIG_EUNSUPPORTED
+    assert rc(d=33, base=L.BASE_MATERN32) == L.GPSIG_EUNSUPPORTED  # tile cells: linear and RBF only
+    assert rc(base=L.BASE_RBF | L.BASE_SEED_MFMA) == L.GPSIG_EUNSUPPORTED
+
+    def route(n1, l1, n2, l2, d, M, order, base="rbf", **kw):
+        r = ops.ho_route(n1, l1, n2, l2, d, M, order, base, **kw)
+        return tuple(r[k] for k in ("tiled", "DP", "W", "nblk", "split", "carry_bytes", "features"))
+    # W: the fewest columns per lane that cover l2, up to 4 (order <= 4), 2 (order 5), 1 (orders 6..8)
+    assert route(4, 45, 2, 40, 3, 8, 8) == (0, 4, 1, 1, 0, 0, False)
+    assert route(4, 70, 2, 65, 3, 8, 8) == (0, 4, 1, 2, 1, 0, False)       # blocks of 63 cells from 65 points
+    assert route(4, 133, 2, 128, 3, 5, 3, "linear") == (0, 4, 2, 1, 0, 0, False)
+    assert route(4, 262, 2, 257, 3, 5, 4) == (0, 4, 4, 2, 1, 0, False)     # 255 cells + a last block of one
+    assert route(4, 261, 2, 256, 7, 5, 5, "linear") == (0, 8, 2, 3, 1, 0, False)  # 19607 coordinates: recursion
+    # five blocks are past SPLIT: the plain kernel, 4 waves x 258 rows x (2 + 3 + 4 + 5 + 6) scans x 4 B of carries
+    assert route(3, 259, 2, 254, 3, 6, 6) == (0, 4, 1, 5, 0, 4 * 258 * 20 * 4, False)
+    # SPLIT up to 2048 workgroups: 12 row groups x 42 sequences x 4, not x 43; GPSIG_HO_SPLIT=0 keeps the plain kernel
+    assert route(48, 68, 42, 65, 2, 6, 6) == (0, 4, 1, 2, 1, 0, False)
+    assert route(48, 68, 43, 65, 2, 6, 6) == (0, 4, 1, 2, 0, 4 * 67 * 20 * 4, False)
+    monkeypatch.setenv("GPSIG_HO_SPLIT", "0")
+    assert route(4, 70, 2, 65, 3, 8, 8) == (0, 4, 1, 2, 0, 4 * 69 * 35 * 4, False)
+    monkeypatch.delenv("GPSIG_HO_SPLIT")
+    # channel paddings 4 / 8 / 16 / 32, increment tiles from 33
+    assert [route(4, 45, 2, 40, d, 4, 3)[:2] for d in (4, 5, 8, 9, 16, 17, 32, 33)] == \
+        [(0, 4), (0, 8), (0, 8), (0, 16), (0, 16), (0, 32), (0, 32), (1, 0)]
+    assert ops.ho_route(13, 30, None, None, 40, 4, 2, "linear", rows=(3, 11))["launches"] == 1
+    assert ops.ho_route(13, 30, None, None, 40, 4, 2, "linear", rows=(3, 3))["launches"] == 0
+    # the carries' 160 KiB: 4 x 292 x 35 x 4 = 163520 B fit, one more row does not
+    assert route(3, 293, 2, 254, 2, 8, 8)[3:6] == (5, 0, 163520)
+    assert rc(n1=3, l1=294, l2=254, d=2, M=8, order=8, r1=3) == L.GPSIG_EUNSUPPORTED and out[5] == 4 * 293 * 35 * 4
+    with pytest.raises(gpsig_amd.GpsigError):
+        ops.ho_route(3, 294, 2, 254, 2, 8, 8)
+    # linear, order >= num_levels, at most 16000 signature coordinates: Python computes signature features
+    assert route(4, 74, 2, 70, 3, 8, 8, "linear") == (0, 4, 1, 2, 1, 0, True)
+    assert route(4, 45, 2, 40, 4, 8, 8, "linear")[-1] is False             # 87380 coordinates
+    monkeypatch.setattr(ops, "SIG_FEATURE_MAX", 0)
+    assert route(4, 74, 2, 70, 3, 8, 8, "linear")[-1] is False
 
 
 def test_graph_capture_refuses_host_tensors_and_kernel_to():

@@ -51,9 +51,10 @@ def test_long_sequences_match_oracle(L, D, M, base, diff):
     (300, 3, 5, 2, "rbf"),       # W = 4: 255 cells per block, 2 blocks
     (300, 4, 5, 3, "linear"),
     (300, 3, 5, 4, "rbf"),
-    (300, 2, 5, 5, "linear"),    # W = 2: 127 cells per block, 3 blocks
+    (300, 2, 5, 5, "linear"),    # order = M, linear, 62 coordinates: signature features + GEMMs, no recursion
     (600, 2, 4, 2, "rbf"),       # 3 blocks
-    (200, 3, 8, 8, "linear"),    # order 8 (exact signature at M = 8): W = 1, 4 blocks of 63 cells
+    (200, 3, 8, 8, "linear"),    # order 8 = M, 9840 coordinates: the feature path too (test_ho_routes_gpu.py runs
+                                 # the recursion at these orders)
 ])
 def test_long_higher_order_matches_oracle(L, D, M, order, base):
     """Higher-order recursion (signature_algs.py:37-74) in column blocks: the exclusive column scans of
