@@ -44,6 +44,7 @@ OUT_LEVELS, OUT_NORM_LEVELS, OUT_NORM_SUM, OUT_RSQRT = 0, 1, 2, 3
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_D = ctypes.c_double
 _SZ = ctypes.c_size_t
 
 SIGNATURES = {
@@ -54,6 +55,11 @@ SIGNATURES = {
     "gpsig_sig_gram": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                             _P, _P, _P, _F, _I, _P, _I, _I, _P, _SZ, _P]),
     "gpsig_sig_diag": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _SZ, _P]),
+    "gpsig_sig_f64_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "gpsig_sig_gram_f64": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                                _P, _P, _P, _D, _I, _P, _I, _I, _P, _SZ, _P]),
+    "gpsig_sig_diag_f64": (_I, [_P, _I, _I, _I, _I, _I, _I, _D, _I, _P, _P, _SZ, _P]),
+    "gpsig_sig_f64_route": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "gpsig_sig_gram_vjp": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I,
                                 _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gpsig_sig_vjp_ho_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I, _I]),

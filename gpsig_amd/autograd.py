@@ -307,49 +307,76 @@ def _unpad_grad(g, l):
     return out
 
 
+def _f64(cfg):
+    """precision="float64": the forward is the float64 kernel (ops.sig_gram_f64 / sig_diag_f64, order 1) and saves
+    no VJP state; the backward is the fp32 VJP launch on the inputs rounded to fp32, recomputing its forward sweep."""
+    return cfg.get("precision", "float32") == "float64"
+
+
+def _state_kw(state):
+    return {} if state is None else {"state": state}
+
+
+def _fwd_gram(cfg, X, Y, **kw):
+    """The forward Gram launch of cfg's precision (raw levels, or the fused epilogue through kw)."""
+    if _f64(cfg):
+        return ops.sig_gram_f64(X, Y, cfg["num_levels"], base=cfg["base"], difference=cfg["difference"], **kw)
+    return ops.sig_gram(X, Y, cfg["num_levels"], order=cfg["order"], base=cfg["base"], difference=cfg["difference"],
+                        **kw)
+
+
+def _fwd_diag(cfg, X, **kw):
+    """The forward diagonal launch of cfg's precision."""
+    if _f64(cfg):
+        return ops.sig_diag_f64(X, cfg["num_levels"], base=cfg["base"], difference=cfg["difference"], **kw)
+    return ops.sig_diag(X, cfg["num_levels"], order=cfg["order"], base=cfg["base"], difference=cfg["difference"],
+                        **kw)
+
+
 class SigGram(torch.autograd.Function):
     """Normalised / raw signature Gram (SignatureKernel.K) with a gfx950 backward."""
 
     @staticmethod
     def forward(ctx, Xs, X2s, scale, cfg):
         M = cfg["num_levels"]
+        f64 = _f64(cfg)
+        wdt = torch.float64 if f64 else torch.float32  # dtype of the kernel's scale, rs and output
         lengths = (Xs.shape[1],) if X2s is None else (max(Xs.shape[1], X2s.shape[1]),)
         if _folded(cfg, X2s, lengths, any(ctx.needs_input_grad[:3])):
             # raw levels (and diagonals) from the kernels, the epilogue in fp64 (the backward differentiates it)
-            kw = dict(order=cfg["order"], base=cfg["base"], difference=cfg["difference"])
             state = None
-            if cfg["order"] == 1 and cfg["difference"]:  # the VJP then skips its forward sweep
+            if cfg["order"] == 1 and cfg["difference"] and not f64:  # the VJP then skips its forward sweep
                 numel = ops.sig_state_numel(Xs.shape[0], None, Xs.shape[1], M)
                 state = _saved_buffer(numel, Xs.device, GRAM_STATE_BYTES)
-            Kr = ops.sig_gram(Xs.detach(), None if X2s is None else X2s.detach(), M, state=state, **kw)
-            sc32 = scale.detach().to(torch.float32)
+            Kr = _fwd_gram(cfg, Xs.detach(), None if X2s is None else X2s.detach(), **_state_kw(state))
+            sc32 = scale.detach().to(wdt)
             ctx.cfg = cfg
             ctx.scale_dtype = scale.dtype
             ctx.state = state
             ctx.folded = True
             if X2s is None:
                 ctx.save_for_backward(Xs, X2s, sc32, Kr, None, None)
-                return _epilogue(Kr.double(), sc32.double(), cfg).to(torch.float32)
-            d1 = ops.sig_diag(Xs.detach(), M, **kw)
-            d2 = ops.sig_diag(X2s.detach(), M, **kw)
+                return _epilogue(Kr.double(), sc32.double(), cfg).to(wdt)
+            d1 = _fwd_diag(cfg, Xs.detach())
+            d2 = _fwd_diag(cfg, X2s.detach())
             ctx.save_for_backward(Xs, X2s, sc32, Kr, d1, d2)
-            return _epilogue_cross(Kr.double(), d1.double(), d2.double(), sc32.double(), cfg).to(torch.float32)
+            return _epilogue_cross(Kr.double(), d1.double(), d2.double(), sc32.double(), cfg).to(wdt)
         ctx.folded = False
         mode = L.OUT_NORM_LEVELS if cfg["return_levels"] else L.OUT_NORM_SUM
-        sc32 = scale.detach().to(torch.float32)
-        kw = dict(order=cfg["order"], base=cfg["base"], difference=cfg["difference"])
+        sc32 = scale.detach().to(wdt)
         rs1 = rs2 = None
         if cfg["normalization"]:
-            rs1 = ops.sig_diag(Xs.detach(), M, jitter=cfg["jitter"], rsqrt=True, **kw)
-            rs2 = rs1 if X2s is None else ops.sig_diag(X2s.detach(), M, jitter=cfg["jitter"], rsqrt=True, **kw)
+            rs1 = _fwd_diag(cfg, Xs.detach(), jitter=cfg["jitter"], rsqrt=True)
+            rs2 = rs1 if X2s is None else _fwd_diag(cfg, X2s.detach(), jitter=cfg["jitter"], rsqrt=True)
         jit = cfg["jitter"] if (cfg["normalization"] and X2s is None) else 0.0
         state = None
-        if any(ctx.needs_input_grad[:3]) and cfg["order"] == 1 and cfg["difference"] and not _no_vjp(cfg):
+        if (any(ctx.needs_input_grad[:3]) and cfg["order"] == 1 and cfg["difference"] and not _no_vjp(cfg)
+                and not f64):
             n2 = None if X2s is None else X2s.shape[0]
             numel = ops.sig_state_numel(Xs.shape[0], n2, Xs.shape[1] if X2s is None else X2s.shape[1], M)
             state = _saved_buffer(numel, Xs.device, GRAM_STATE_BYTES)
-        out = ops.sig_gram(Xs.detach(), None if X2s is None else X2s.detach(), M, rs1=rs1, rs2=rs2, scale=sc32,
-                           jitter=jit, out_mode=mode, state=state, **kw)
+        out = _fwd_gram(cfg, Xs.detach(), None if X2s is None else X2s.detach(), rs1=rs1, rs2=rs2, scale=sc32,
+                        jitter=jit, out_mode=mode, **_state_kw(state))
         ctx.state = state
         ctx.cfg = cfg
         ctx.scale_dtype = scale.dtype
@@ -469,7 +496,7 @@ class SigDiag(torch.autograd.Function):
     def forward(ctx, Xs, cfg):
         ctx.cfg = cfg
         ctx.save_for_backward(Xs)
-        return ops.sig_diag(Xs.detach(), cfg["num_levels"], cfg["order"], cfg["base"], cfg["difference"])
+        return _fwd_diag(cfg, Xs.detach())
 
     @staticmethod
     def backward(ctx, gout):

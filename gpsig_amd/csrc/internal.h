@@ -25,6 +25,11 @@ size_t fo_split_bytes(int l1, int l2, int DP, int M);
 template <int DP, int M>
 int sig_fo_launch_dpm(const SigArgs &a, int seed, long long nblocks, hipStream_t s);  // sig_fo_inst.hip
 
+// ---- sig_f64_inst.hip: the float64 first-order kernels of one level count
+struct F64Args;  // sig_f64.h
+template <int M>
+int sig_f64_launch_m(const F64Args &a, int W, int LP, long long nblocks, hipStream_t s);
+
 // ---- sig_fo_mf.hip: the matrix-core wide Gram
 int mf_records(const float *X, int n, int l, int d, float *R, hipStream_t s);
 size_t mf_records_bytes(int n, int l, int d);

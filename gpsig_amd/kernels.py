@@ -15,6 +15,11 @@ tensors here), and base kernels without a gfx950 seed (Cosine, Poly, Mix, Spectr
 kernels (SignatureMatern12 / Laplace / Exponential, SignatureMatern32, SignatureMatern52) have a forward
 seed: K, K_norms, Kdiag, K_seq_n_seq_covs and the low-rank mode work; their gradients and the
 inducing-tensor kernels (K_tens*) raise NotImplementedError.
+
+The kernels compute in float32.  The trailing keyword ``precision="float64"`` (not a reference argument) evaluates
+K, Kdiag, K_norms and K_seq_n_seq_covs of an order-1 kernel in float64 (gpsig_sig_gram_f64 / gpsig_sig_diag_f64,
+up to 513 points per sequence); its gradients are the fp32 VJP kernels', and order > 1 and K_tens* raise
+NotImplementedError there.
 """
 from __future__ import annotations
 
@@ -52,8 +57,11 @@ class SignatureKernel:
 
     def __init__(self, input_dim, num_features, num_levels, active_dims=None, variances=1, lengthscales=1, order=1,
                  normalization=True, difference=True, num_lags=None, low_rank=False, num_components=50,
-                 rank_bound=None, sparsity='sqrt', name=None, jitter=DEFAULT_JITTER):
+                 rank_bound=None, sparsity='sqrt', name=None, jitter=DEFAULT_JITTER, precision="float32"):
         # kernels.py:54-89
+        if precision not in ("float32", "float64"):
+            raise ValueError("precision must be 'float32' or 'float64', got %r" % (precision,))
+        self.precision = precision
         self.input_dim = input_dim
         self.active_dims = active_dims
         self.name = name
@@ -63,6 +71,9 @@ class SignatureKernel:
         self.order = num_levels if (order <= 0 or order >= num_levels) else order
         if self.order != 1 and low_rank:
             raise NotImplementedError('Higher-order algorithms not compatible with low-rank mode (yet).')
+        if self.order != 1 and precision == "float64":
+            raise NotImplementedError('precision="float64" evaluates the first-order kernels (order=1) only; the '
+                                      'higher-order recursion has no float64 kernel')
         self.normalization = normalization
         self.difference = difference
         self.jitter = float(jitter)
@@ -163,10 +174,20 @@ class SignatureKernel:
             X, _ = self._slice(X)
         N = X.shape[0]
         X = X.reshape(N, int(np.prod(X.shape[1:])) // self.num_features, self.num_features)  # (N = 0 allowed)
+        if self._f64():  # lags and lengthscale scaling in float64 whatever the input's dtype
+            X = X.to(torch.float64)
         return self._apply_scaling_and_lags_to_sequences(X)
 
+    def _f64(self):
+        """precision="float64" outside the low-rank mode (which is torch float64 already)."""
+        return self.precision == "float64" and not self.low_rank
+
+    def _wdt(self):
+        """dtype the kernels compute and return in."""
+        return torch.float64 if self._f64() else torch.float32
+
     def _scale_vec(self, device):
-        return (self.sigma * self.variances).to(device=device, dtype=torch.float32)
+        return (self.sigma * self.variances).to(device=device, dtype=self._wdt())
 
     def _out_dtype(self, X):
         return X.dtype if (isinstance(X, torch.Tensor) and X.is_floating_point()) else torch.float64
@@ -174,7 +195,8 @@ class SignatureKernel:
     # ------------------------------------------------------------------ algorithm seam (kernels.py:190-341)
     def _cfg(self, return_levels=False):
         return dict(num_levels=self.num_levels, order=self.order, base=self.base, difference=self.difference,
-                    normalization=self.normalization, jitter=self.jitter, return_levels=bool(return_levels))
+                    normalization=self.normalization, jitter=self.jitter, return_levels=bool(return_levels),
+                    precision=self.precision)
 
     def _K_seq_diag(self, X):
         """(N,L,D) scaled -> (num_levels+1, N) unnormalised diagonal (kernels.py:190-207); differentiable."""
@@ -182,9 +204,13 @@ class SignatureKernel:
 
     def _K_seq(self, X, X2=None):
         """(N,L,D) scaled -> (num_levels+1, N, N2) unnormalised per-level Gram (kernels.py:209-238)."""
+        if self._f64():
+            return ops.sig_gram_f64(X, X2, self.num_levels, self.base, self.difference)
         return ops.sig_gram(X, X2, self.num_levels, self.order, self.base, self.difference)
 
     def _rsqrt_diag(self, X):
+        if self._f64():
+            return ops.sig_diag_f64(X, self.num_levels, self.base, self.difference, jitter=self.jitter, rsqrt=True)
         return ops.sig_diag(X, self.num_levels, self.order, self.base, self.difference, jitter=self.jitter,
                             rsqrt=True)
 
@@ -316,11 +342,14 @@ class SignatureKernel:
             Kd = torch.stack([(p ** 2).sum(-1) for p in self._K_seq_lr_feat(Xs)], 0)
             Kd = Kd * (self.sigma * self.variances).to(Xs.device, Kd.dtype)[:, None]
             return (Kd if return_levels else Kd.sum(0)).to(dt)
-        Kd = self._K_seq_diag(Xs) * (self.sigma * self.variances).to(Xs.device, torch.float32)[:, None]
+        Kd = self._K_seq_diag(Xs) * (self.sigma * self.variances).to(Xs.device, self._wdt())[:, None]
         return (Kd if return_levels else Kd.sum(0)).to(dt)
 
     # ------------------------------------------------------------------ inducing tensors (kernels.py:544-704)
     def _need_tensor_seed(self, what):
+        if self._f64():
+            raise NotImplementedError(f"{type(self).__name__}.{what}: the inducing-tensor kernels have no float64 "
+                                      'kernel; precision="float64" covers K, Kdiag, K_norms and K_seq_n_seq_covs')
         if ops.forward_only(self.base):
             raise NotImplementedError(f"{type(self).__name__}.{what}: the inducing-tensor kernels have no "
                                       f"{self.base} seed in this build (RBF and linear only); inducing sequences "
@@ -381,8 +410,8 @@ class SignatureKernel:
         return self._K_tens_lr_feat(Zs, increments, nys, seeds), self._K_seq_lr_feat(Xs, nys, seeds)
 
     def _sv(self, device):
-        """sigma * variances as float32 on device, differentiable in variances."""
-        return (self.sigma * self.variances).to(device, torch.float32)
+        """sigma * variances in the kernels' dtype on device, differentiable in variances."""
+        return (self.sigma * self.variances).to(device, self._wdt())
 
     def _gram_levels(self, Xs, X2s=None):
         """Normalised (if self.normalization) per-level K(X[, X2]) x sigma*variances, differentiable."""

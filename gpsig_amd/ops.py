@@ -222,6 +222,95 @@ def sig_gram(X: torch.Tensor, Y: torch.Tensor | None, num_levels: int, order: in
     return out
 
 
+# ----------------------------------------------------------------------------- float64 evaluation (order 1)
+F64_MAX_POINTS = 513  # one column block: 512 cell columns (513 points with difference=True, 512 without)
+
+
+def _f64(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.float64).contiguous() if (t.dtype != torch.float64 or not t.is_contiguous()) else t
+
+
+def _check_f64(rc: int, what: str, l2: int, difference: bool, num_levels: int) -> None:
+    if rc == L.GPSIG_EUNSUPPORTED:
+        raise L.GpsigError(f"{what}: the float64 kernels take sequences of up to {F64_MAX_POINTS} points "
+                           f"({F64_MAX_POINTS - 1} with difference=False) and up to 8 levels, RBF / linear / Matern base "
+                           f"kernels (got {l2} points, difference={bool(difference)}, {num_levels} levels; code {rc})")
+    L.check(rc, what)
+
+
+def f64_route(l1: int, l2: int | None, num_levels: int, difference: bool = True, diag: bool = False) -> dict:
+    """What sig_gram_f64 / sig_diag_f64 run for a shape (gpsig_sig_f64_route: host only): W columns per lane, LP
+    lanes per pair.  l2 None: the symmetric K(X) (diag=True: the diagonal).  Raises GpsigError where the call would."""
+    import ctypes
+    sym = l2 is None
+    pm = L.PAIRS_DIAG if diag else (L.PAIRS_UPPER if sym else L.PAIRS_RECT)
+    if sym:
+        l2 = l1
+    out = (ctypes.c_int * 2)()
+    rc = L.load().gpsig_sig_f64_route(l1, l2, num_levels, int(bool(difference)), pm, out)
+    _check_f64(rc, "gpsig_sig_f64_route", l2, difference, num_levels)
+    return {"W": out[0], "LP": out[1]}
+
+
+def sig_diag_f64(X: torch.Tensor, num_levels: int, base="rbf", difference: bool = True, jitter: float = 0.0,
+                 rsqrt: bool = False) -> torch.Tensor:
+    """sig_diag at order 1 in float64 (gpsig_sig_diag_f64): (num_levels+1, n) float64, no fp32 rounding of X."""
+    _require_cuda(X)
+    lib = L.load()
+    X = _f64(X)
+    n, l, d = X.shape
+    out = torch.empty((num_levels + 1, n), dtype=torch.float64, device=X.device)
+    if n == 0:
+        return out
+    ws = workspace(X.device, lib.gpsig_sig_f64_workspace_bytes(n, l, n, l, d))
+    rc = lib.gpsig_sig_diag_f64(X.data_ptr(), n, l, d, num_levels, base_kind(base), int(bool(difference)),
+                                float(jitter), L.OUT_RSQRT if rsqrt else L.OUT_LEVELS, out.data_ptr(), ws.data_ptr(),
+                                ws.numel(), _stream(X.device))
+    _check_f64(rc, "gpsig_sig_diag_f64", l, difference, num_levels)
+    return out
+
+
+def sig_gram_f64(X: torch.Tensor, Y: torch.Tensor | None, num_levels: int, base="rbf", difference: bool = True,
+                 rows: tuple | None = None, rs1=None, rs2=None, scale=None, jitter: float = 0.0,
+                 out_mode: int = L.OUT_LEVELS, out: torch.Tensor | None = None,
+                 out_row0: int | None = None) -> torch.Tensor:
+    """sig_gram at order 1 in float64 (gpsig_sig_gram_f64): same arguments and shapes, float64 inputs (converted
+    without fp32 rounding), rs1 / rs2 / scale and the output in float64."""
+    _require_cuda(X, Y, rs1, rs2, scale)
+    lib = L.load()
+    X = _f64(X)
+    sym = Y is None
+    Y = X if sym else _f64(Y)
+    n1, l1, d = X.shape
+    n2, l2, d2 = Y.shape
+    if d2 != d:
+        raise ValueError("X and Y must have the same channel count")
+    r0, r1 = (0, n1) if rows is None else rows
+    if out_row0 is None:
+        out_row0 = r0
+    if out is None:
+        nrows = r1 - out_row0
+        shape = (nrows, n2) if out_mode == L.OUT_NORM_SUM else (num_levels + 1, nrows, n2)
+        out = torch.empty(shape, dtype=torch.float64, device=X.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float64 tensor")
+    out_rows = out.shape[-2]
+    if n1 == 0 or n2 == 0 or r1 == r0:  # an empty batch
+        return out
+    if rs1 is not None:
+        rs1, rs2 = _f64(rs1), _f64(rs2)
+    if scale is not None:
+        scale = _f64(scale)
+    pm = L.PAIRS_UPPER if sym else L.PAIRS_RECT
+    ws = workspace(X.device, lib.gpsig_sig_f64_workspace_bytes(n1, l1, n2, l2, d))
+    rc = lib.gpsig_sig_gram_f64(X.data_ptr(), n1, l1, Y.data_ptr(), n2, l2, d, num_levels, base_kind(base),
+                                int(bool(difference)), pm, r0, r1, _ptr(rs1), _ptr(rs2), _ptr(scale), float(jitter),
+                                out_mode, out.data_ptr(), out_row0, out_rows, ws.data_ptr(), ws.numel(),
+                                _stream(X.device))
+    _check_f64(rc, "gpsig_sig_gram_f64", l2, difference, num_levels)
+    return out
+
+
 def ho_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_levels: int, order: int, base="rbf",
              difference: bool = True, diag: bool = False, rows: tuple | None = None) -> dict:
     """What sig_gram / sig_diag at order >= 2 would run for a shape (gpsig_sig_ho_route: host only, no launch, no

@@ -363,6 +363,33 @@ int gpsig_sig_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, in
                        int difference, int pair_mode, int row_begin, int row_end, int *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Float64 evaluation of the first-order Gram and diagonal (order 1): double inputs, double arithmetic, double
+ * outputs, for K that goes into a Cholesky factorisation, for unstandardised data (point offsets of many
+ * lengthscales) and as an on-device reference for the fp32 kernels.  Arguments, pair modes, row window, out modes
+ * and epilogue as gpsig_sig_gram / gpsig_sig_diag (rs1, rs2, scale, jitter and out in double; rs1 / rs2 from
+ * gpsig_sig_diag_f64 with GPSIG_OUT_RSQRT).  Any channel count (a runtime channel loop over channel-major fp64
+ * records in the workspace); base kinds RBF, linear and the three Matern; difference 1 or 0; num_levels <= 8;
+ * one column block of at most 512 cell columns: l2 <= 513 with difference = 1, l2 <= 512 without (l1 is not
+ * bounded in RECT mode: rows are streamed).
+ * Returns, each before any launch: GPSIG_EINVAL for bad sizes or pointers; GPSIG_EUNSUPPORTED for num_levels > 8,
+ * columns past the cap, the GPSIG_BASE_SEED_MFMA / GPSIG_GRAM_SPLIT flags and unknown base kinds;
+ * GPSIG_EWORKSPACE below gpsig_sig_f64_workspace_bytes (the records of X and of Y, each 16 n l d bytes rounded up
+ * to 256; 0 for sizes no call accepts). */
+size_t gpsig_sig_f64_workspace_bytes(int n1, int l1, int n2, int l2, int d);
+int gpsig_sig_gram_f64(const double *X, int n1, int l1, const double *Y, int n2, int l2, int d, int num_levels,
+                       int base_kind, int difference, int pair_mode, int row_begin, int row_end,
+                       const double *rs1, const double *rs2, const double *scale, double jitter, int out_mode,
+                       double *out, int out_row0, int out_rows, void *workspace, size_t workspace_bytes,
+                       gpsig_stream_t stream);
+int gpsig_sig_diag_f64(const double *X, int n, int l, int d, int num_levels, int base_kind, int difference,
+                       double jitter, int out_mode, double *out, void *workspace, size_t workspace_bytes,
+                       gpsig_stream_t stream);
+/* What the two calls above run for a shape (host only): out[0] = W columns per lane, out[1] = LP lanes per pair,
+ * by the cell columns c = l2 - 1 (difference = 1) or l2: c <= 64 (4, 16), <= 128 (4, 32), <= 256 (4, 64),
+ * <= 512 (8, 64).  GPSIG_OK, GPSIG_EINVAL or GPSIG_EUNSUPPORTED as the calls (out is (0, 0) then). */
+int gpsig_sig_f64_route(int l1, int l2, int num_levels, int difference, int pair_mode, int *out /* W, LP */);
+
+/* ---------------------------------------------------------------------------------------------
  * Truncated signatures (replaces iisignature.sig behind iisignature_tensorflow.Sig,
  * gpsig/iisignature_tensorflow.py:87, used by the VOSF Kuf, gpsig/inducing_variables_vosf.py:120-146).
  * X (n, l, d) -> out (n, gpsig_signature_channels(d, depth)): levels 1..depth, each flattened
