@@ -396,10 +396,14 @@ using GenSeed = std::conditional_t<seed_is_radial(SEED), RadialSeed<DP, W, SEED>
 // with the per-row work cut to what the recursion needs and laid out for v_pk_* instructions.
 // With p_ij = <y_j, dx_i> - g_i (g_i from the feature record), c_ij = <dx_i, dy_j> and
 // q_ij = <x_i - y_j, dy_j> - |dy_j|^2/2, the cell is k(x_i,y_j) (Ep Eq + (1 + Ep)(1 + Eq) Ec),
-// E* = expm1(*), and both row-to-row quantities follow from what the cell already computed:
-//   k(x_{i+1}, y_j) = k(x_i, y_j) (1 + Ep_ij)          q_{i+1,j} = q_ij + c_ij
-//   Eq_{i+1,j} = Eq_ij + Ec_ij + Eq_ij Ec_ij           (= expm1(q_ij + c_ij), no cancellation)
-// so a row costs two packed dots, two polynomial expm1 (p, c) and a few FMAs per column pair: no
+// E* = expm1(*).  The cell is evaluated in increment form (cells()): with the row increment
+// d_ij = k(x_{i+1}, y_j) - k(x_i, y_j) = k Ep and w_ij = Ec (1 + Eq) its two terms are d Eq + (k + d) w, and
+// both row-to-row quantities are sums of what the cell already computed:
+//   k(x_{i+1}, y_j) = k(x_i, y_j) + d_ij               q_{i+1,j} = q_ij + c_ij
+//   Eq_{i+1,j} = Eq_ij + w_ij                          (= expm1(q_ij + c_ij), no cancellation)
+// d itself chains along the columns (d_{i,j+1} = d_ij + dM_ij: dM is the second difference of the k grid),
+// so a row costs one packed dot and one polynomial expm1 (c) per column pair, the dot and expm1 of p for
+// the lane's first pair, and six packed operations per pair: no
 // exp.  k and Eq are re-evaluated exactly from x_{i+1} - y_j on anchor rows (every ANCHOR rows), so
 // rounding drift is bounded by ANCHOR steps.  When |p| or |c| of some cell of the wave reaches
 // EM1_TAU (a wave-uniform branch), the next row is evaluated exactly and those cells take the plain
@@ -420,7 +424,11 @@ struct RbfSeedPk {
   static constexpr int YR = YG ? 1 : W2;
   f2 y[YR][DP], dy[W2][DP], hdy[W2];
   f2 Eq[W2], kc[W2];  // expm1(q_ij), k(x_i, y_j)
-  float kcR;          // next lane's kc of its first column
+  // u_ij = k(x_i, y_j) - k(x_0, y_j), the running sum of the rows' increments d, and du = d of the row just
+  // evaluated (exact rows: the difference of the exact k rows).  The exclusive 2-D prefix of the cells
+  // telescopes to S_1(i, j) = u_ij - u_i0 (sig_fo.h, levels); u is advanced by step_u() once row i's levels
+  // have read it.  Dead where the kernel scans level 1 instead.
+  f2 u[W2], du[W2];
   bool valid_last;
   bool clo = false;   // every |c_ij| of the wave < EM1_LO_TAU: Ec by the cubic (bound_c)
   const float *fyb;   // YG: the block's point records, this lane's first column, the last point
@@ -467,7 +475,8 @@ struct RbfSeedPk {
 #pragma unroll
     for (int k = 0; k < DP; ++k) x0[k] = fx[k];
     exact(x0, Eq, kc);
-    kcR = lane_next(kc[0][0]);
+#pragma unroll
+    for (int w2 = 0; w2 < W2; ++w2) u[w2] = du[w2] = splat2(0.0f);
   }
 
   // |c_ij| = |<dx_i, dy_j>| <= 2 sqrt(hdx_i hdy_j) (Cauchy-Schwarz on the records' |d|^2/2): when the
@@ -548,12 +557,10 @@ struct RbfSeedPk {
     return a;
   }
 
-  // The seed of row i shared by row() and row_hot(): the dots c (every pair), p from pair 0's p0 by the
-  // column recurrence described at row(), the polynomials, and the product-form cells into dM from the
-  // current kc, Eq (neither is written).  Returns the lane's range-check value max |p|, |c|.
+  // The dots of row i shared by row() and hot_dots(): c (every pair) and p, from pair 0's p0 by the column
+  // recurrence described at row().  Returns the lane's range-check value max |p|, |c|.
   template <bool CLO>
-  GPSIG_DEV float cells(const Row &rd, f2 p0, f2 (&p)[W2], f2 (&c)[W2], f2 (&Ec)[W2], f2 (&Ep)[W2],
-                        f2 (&dM)[W2]) const {
+  GPSIG_DEV float dots(const Row &rd, f2 p0, f2 (&p)[W2], f2 (&c)[W2]) const {
     // channel-major, so the pairs' dots (each a serial chain of packed FMAs) are written interleaved: a
     // packed result read by the very next instruction costs a wait state
 #pragma unroll
@@ -565,82 +572,105 @@ struct RbfSeedPk {
     p[0] = p0;
 #pragma unroll
     for (int w2 = 1; w2 < W2; ++w2) p[w2] = p[w2 - 1] + c[w2 - 1];
-    if constexpr (CLO)
-      em1_lo2_n<W2>(c, Ec);
-    else
-      em1_small2_n<W2>(c, Ec);
-    // Ep[1] = Ep[0] + t with Ep[0] = p P(p) is the FMA p P(p) + t, written out: left as a sum it is fused
-    // or not by where the branches of the row loop fall (the former two-row loop of W <= 4 fused it on odd
-    // rows only; the W >= 8 loops on every row)
-    const f2 Pp = em1_small2_poly(p[0]);
-    Ep[0] = Pp * p[0];
     float mx = 0.0f;
 #pragma unroll
-    for (int w2 = 0; w2 < W2; ++w2) {
-      const f2 t = fma2(Ep[w2], Ec[w2], Ec[w2]);  // (1 + Ep) Ec
-      if (w2 + 1 < W2) Ep[w2 + 1] = w2 == 0 ? fma2(Pp, p[0], t) : Ep[w2] + t;
-      const f2 t2 = fma2(Eq[w2], t, t);
-      {
-        // the cell is a rounded product: never contracted into the level recursion's C_1 += dM
-#pragma clang fp contract(off)
-        dM[w2] = kc[w2] * fma2(Ep[w2], Eq[w2], t2);
-      }
+    for (int w2 = 0; w2 < W2; ++w2)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        // CLO: every Ec is in the cubic's range a priori, and the pairs after the first take Ep by the exact
-        // chain Ep' = Ep + (1 + Ep) Ec, so only the first pair's p meets a polynomial
+        // CLO: every Ec is in the cubic's range a priori, and the pairs after the first never form Ep (their
+        // increment d follows the exact chain, cells()), so only the first pair's p meets a polynomial
         if constexpr (CLO) {
           if (w2 == 0) mx = __builtin_fmaxf(mx, __builtin_fabsf(p[w2][h]));
         } else {
           mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
         }
       }
-    }
     return mx;
   }
 
-  // Row i of the hot loop (sig_fo.h), p0 = p0_dot(rd): the cells into dM, then kc, Eq and kcR advanced in
-  // place by the row-to-row recurrences.  Returns true, with kc, Eq and kcR untouched, when a cell of the
-  // wave is outside the polynomial range: the caller then runs row() on the same record (the slow path),
-  // which recomputes the same seed.  No exact evaluation lives here, so the loop around it carries its
-  // state in place.
+  // The cells of row i in increment form, from its dots c and pair 0's p0 and the current kc, Eq.  With
+  // d_ij = k(x_{i+1}, y_j) - k(x_i, y_j) = kc Ep and w = Ec (1 + Eq) the cell's two terms read
+  //   dM = kc Ep Eq + kc (1 + Ep) (1 + Eq) Ec = d Eq + kn w,   kn = kc + d,   Eqn = Eq + w
+  // (kn, Eqn: the next row's kc, Eq), and d chains along the columns exactly: dM is the second difference
+  // of the k grid, so d_{i,j+1} = d_ij + dM_ij.  Only pair 0 forms Ep (d = kc Ep); pairs 1 .. W/2-1 follow
+  // in-lane, six packed operations per pair.  d is left in du for the level-1 prefix (u).
+  // kn / Eqn may be kc / Eq themselves (the hot row advances them in place).
   template <bool CLO>
-  GPSIG_DEV bool row_hot(const Row &rd, f2 p0, f2 (&dM)[W2]) {
-    f2 p[W2], c[W2], Ec[W2], Ep[W2];
-    const float mx = cells<CLO>(rd, p0, p, c, Ec, Ep, dM);
-    if (__builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0) return true;
+  GPSIG_DEV void cells(f2 p0, const f2 (&c)[W2], f2 (&dM)[W2], f2 (&kn)[W2], f2 (&Eqn)[W2]) {
+    f2 Ec[W2];
+    if constexpr (CLO)
+      em1_lo2_n<W2>(c, Ec);
+    else
+      em1_small2_n<W2>(c, Ec);
+    const f2 Pp = em1_small2_poly(p0);
+    {
+      // every product below is rounded: the sums that take d = kc Ep (kc + d, u + d, d + dM) would otherwise
+      // be fused with it or not by where the branches of the row loop fall
+#pragma clang fp contract(off)
+      f2 d = kc[0] * (Pp * p0);
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2) {
+        const f2 k1 = kc[w2] + d;
+        const f2 w = fma2(Ec[w2], Eq[w2], Ec[w2]);  // Ec (1 + Eq)
+        const f2 m = fma2(d, Eq[w2], k1 * w);
+        du[w2] = d;
+        dM[w2] = m;
+        kn[w2] = k1;
+        Eqn[w2] = Eq[w2] + w;
+        if (w2 + 1 < W2) d = d + m;
+      }
+    }
+  }
+
+  // u += du: the level-1 prefix state after row i's levels have read it (sig_fo.h)
+  GPSIG_DEV void step_u() {
 #pragma unroll
     for (int w2 = 0; w2 < W2; ++w2) {
-      // Eq + Ec is a rounded sum: Ec's final product x P(x) is not contracted into it
 #pragma clang fp contract(off)
-      kc[w2] = fma2(kc[w2], Ep[w2], kc[w2]);
-      Eq[w2] = fma2(Eq[w2], Ec[w2], Eq[w2] + Ec[w2]);
+      u[w2] = u[w2] + du[w2];
     }
-    kcR = lane_next(kc[0][0]);
-    return false;
+  }
+
+  // Row i of the hot loop (sig_fo.h), p0 = p0_dot(rd), in two calls with the caller's one branch between them.
+  // hot_dots: the dots c and the range check; true when a cell of the wave is outside the polynomial range.
+  // The caller then leaves the run with no state written and runs row() on the same record (the slow path),
+  // which recomputes the same dots.  hot_cells: the cells into dM, with kc and Eq advanced in place by the
+  // row-to-row recurrences (the increment form needs the next row's k for the cell itself, so the cells
+  // cannot precede the check as long as kc is carried in place).  No exact evaluation lives here, so the
+  // loop around the two carries its state in its registers.
+  template <bool CLO>
+  GPSIG_DEV bool hot_dots(const Row &rd, f2 p0, f2 (&c)[W2]) const {
+    f2 p[W2];
+    const float mx = dots<CLO>(rd, p0, p, c);
+    return __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
+  }
+  template <bool CLO>
+  GPSIG_DEV void hot_cells(f2 p0, const f2 (&c)[W2], f2 (&dM)[W2]) {
+    cells<CLO>(p0, c, dM, kc, Eq);
   }
 
   // Cells of row i into dM.  anch (wave-uniform): the next row's state is re-evaluated exactly
   // instead of by the recurrences.
   //
   // Column recurrence of the p side: p_{i,j+1} - p_ij = <y_{j+1} - y_j, dx_i> = c_ij, so
-  //   p_{i,j+1} = p_ij + c_ij,   Ep_{i,j+1} = expm1(p_ij + c_ij) = Ep_ij + (1 + Ep_ij) Ec_ij
-  // and (1 + Ep) Ec is a term the cell needs anyway.  Only column pair 0 (the lane's columns 0 and
-  // W/2) takes the dot and the polynomial; pairs 1 .. W/2-1 follow in-lane (two operations each instead
-  // of D + 6).  Rows with a cell outside the polynomial range re-evaluate every Ep directly (slow path).
+  //   p_{i,j+1} = p_ij + c_ij
+  // and only column pair 0 (the lane's columns 0 and W/2) takes the dot and the polynomial; p of pairs
+  // 1 .. W/2-1 serves the range check and the slow path alone (the cells chain d, see cells()).  Rows with
+  // a cell outside the polynomial range re-evaluate every Ep directly (slow path).
   // CLO: the pair block's |c| bound holds (bound_c): Ec by the cubic, and only |p| is range-checked.
   template <bool CLO = false>
   GPSIG_DEV void row(const Row &rd, bool anch, f2 (&dM)[W2]) {
-    f2 p[W2], c[W2], Ec[W2], Ep[W2];
-    const float mx = cells<CLO>(rd, p0_dot(rd), p, c, Ec, Ep, dM);
+    f2 p[W2], c[W2], kr[W2], Eqr[W2];
+    const float mx = dots<CLO>(rd, p0_dot(rd), p, c);
     const bool slow = __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
+    cells<CLO>(p[0], c, dM, kr, Eqr);
     if (anch || slow) {
       f2 Eqn[W2], kn[W2];
       next_exact(rd, Eqn, kn);
-      const float knR = lane_next(kn[0][0]);
       if (slow) {
-        // a cell outside the polynomial range may have spoilt the chained Ep of the pairs after it:
-        // every in-range cell is re-evaluated from its own p, the others take the corner difference
+        // a cell outside the polynomial range spoils the chained d of the pairs after it: every in-range
+        // cell is re-evaluated from its own p in the product form, the others take the corner difference
+        const float knR = lane_next(kn[0][0]), kcR = lane_next(kc[0][0]);  // the next lane's first column
         f2 Epd[W2], Ecd[W2];
         em1_small2_n<W2>(p, Epd);
         em1_small2_n<W2>(c, Ecd);
@@ -661,18 +691,17 @@ struct RbfSeedPk {
       }
 #pragma unroll
       for (int w2 = 0; w2 < W2; ++w2) {
+        du[w2] = kn[w2] - kc[w2];
         Eq[w2] = Eqn[w2];
         kc[w2] = kn[w2];
       }
-      kcR = knR;
     } else {
-      // row-to-row recurrences in place (the cells above were the last readers of kc and Eq)
+      // row-to-row recurrences (the cells above were the last readers of kc and Eq)
 #pragma unroll
       for (int w2 = 0; w2 < W2; ++w2) {
-        kc[w2] = fma2(kc[w2], Ep[w2], kc[w2]);
-        Eq[w2] = fma2(Eq[w2], Ec[w2], Eq[w2] + Ec[w2]);
+        kc[w2] = kr[w2];
+        Eq[w2] = Eqr[w2];
       }
-      kcR = lane_next(kc[0][0]);
     }
   }
 
@@ -704,7 +733,8 @@ struct RbfSeedPk {
     }
   }
 
-  // Cells of row i from its precomputed p, c (column pairs).
+  // Cells of row i from its precomputed p, c (column pairs): every pair has its own Ep, so d = kc Ep per
+  // pair and the increment form of cells() without the chain.
   GPSIG_DEV void row_pc(const Row &rd, bool anch, const f2 (&p)[W2], const f2 (&c)[W2], f2 (&dM)[W2]) {
     f2 Eqn[W2], kn[W2];
     f2 Ep[W2], Ec[W2];
@@ -713,19 +743,25 @@ struct RbfSeedPk {
     float mx = 0.0f;
 #pragma unroll
     for (int w2 = 0; w2 < W2; ++w2) {
-      f2 t = fma2(Ep[w2], Ec[w2], Ec[w2]);
-      t = fma2(Eq[w2], t, t);
-      dM[w2] = kc[w2] * fma2(Ep[w2], Eq[w2], t);
-      kn[w2] = fma2(kc[w2], Ep[w2], kc[w2]);
-      Eqn[w2] = fma2(Eq[w2], Ec[w2], Eq[w2] + Ec[w2]);
+#pragma clang fp contract(off)
+      const f2 d = kc[w2] * Ep[w2];
+      const f2 w = fma2(Ec[w2], Eq[w2], Ec[w2]);
+      kn[w2] = kc[w2] + d;
+      dM[w2] = fma2(d, Eq[w2], kn[w2] * w);
+      Eqn[w2] = Eq[w2] + w;
+      du[w2] = d;
 #pragma unroll
       for (int h = 0; h < 2; ++h) mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(p[w2][h])), __builtin_fabsf(c[w2][h]));
     }
     const bool slow = __builtin_amdgcn_ballot_w64(mx >= EM1_TAU) != 0;
-    if (anch || slow) next_exact(rd, Eqn, kn);
-    const float knR = lane_next(kn[0][0]);
+    if (anch || slow) {
+      next_exact(rd, Eqn, kn);
+#pragma unroll
+      for (int w2 = 0; w2 < W2; ++w2) du[w2] = kn[w2] - kc[w2];
+    }
     if (slow) {
       // corner difference k11 - k10 - k01 + k00 for the cells outside the polynomial range
+      const float knR = lane_next(kn[0][0]), kcR = lane_next(kc[0][0]);
 #pragma unroll
       for (int w = 0; w < W; ++w) {
         const int w2 = w % W2, h = w / W2;
@@ -743,7 +779,6 @@ struct RbfSeedPk {
       Eq[w2] = Eqn[w2];
       kc[w2] = kn[w2];
     }
-    kcR = knR;
   }
 };
 

@@ -162,9 +162,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP
 #pragma unroll
       for (int w2 = 0; w2 < W2; ++w2) C[m][w2] = splat2(0.0f);
 
-    // One row: seed cells (do_row below, or the hot loop's row_hot), then the level recursion (levels).
-    // S_m = exclusive prefix over (rows < i, cols < j) of R_m = exclusive scan over j of C_m; the M-1 scans
-    // are independent and interleave.
+    // One row: seed cells (do_row below, or the hot loop's hot_cells), then the level recursion (levels).
+    // S_m = exclusive prefix over (rows < i, cols < j) of R_m = exclusive scan over j of C_m; the scans of a
+    // row are independent and interleave.
+    //
+    // U1 (packed RBF seed, one column block by construction: LP < 64): level 1's prefix is not scanned.
+    // R_1 = dM is the second difference of the k grid, so its exclusive 2-D prefix telescopes to
+    //   S_1(i, j) = u_ij - u_i0,   u_ij = k(x_i, y_j) - k(x_0, y_j)
+    // and u is the running sum of the row increments d the seed forms anyway (RbfSeedPk::u): one broadcast of
+    // the group's first column and a subtraction per column pair replace level 1's in-lane prefix, its share
+    // of the cross-lane scan, the offsets and C_1 += dM.  Every lane of a group subtracts the same lane's
+    // value, so the result does not depend on the group's slot.  C_1 is then read by nobody (K_1 is closed
+    // form too); the saved-state launch keeps C_1 += dM for the state it stores, beside the same closed form.
+    // The column-block path (LP = 64) would need column 0 of the sequence, not of the block, and the split
+    // consumer has no k: both scan level 1 like the other seeds.
+    constexpr bool U1 = PK && SPLIT == 0 && LP < 64;
+    constexpr int M0 = U1 ? 1 : 0;                  // levels 1 .. M0 take their prefix in closed form
+    constexpr int NSC = ML - M0 > 0 ? ML - M0 : 1;  // scanned levels (array size, at least 1)
+    [[maybe_unused]] const int bc0 = 4 * (lane - gl);  // ds_bpermute address of the group's first lane
     using Rec = typename FoRec<WIDE, PK, PSeed, DP, W>::type;
     auto levels = [&](int i, const f2 (&dM)[W2]) {
       if constexpr (SPLIT == 1) {
@@ -179,20 +194,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP
       // S_m(column) = E_k + (b, b + H_lo) with b the exclusive cross-lane prefix of T = H_lo + H_hi.
       // The lane totals of the M-1 levels are scanned across the group together.
       f2 E[ML][W2 + 1];
-      float T[ML], base[ML];
+      float T[ML], base[NSC];  // base[m - M0]: level m + 1's lane total, then its inclusive cross-lane prefix
 #pragma unroll
-      for (int m = 0; m + 1 < M; ++m) {
+      for (int m = M0; m + 1 < M; ++m) {
         E[m][1] = C[m][0];
 #pragma unroll
         for (int k = 2; k <= W2; ++k) E[m][k] = E[m][k - 1] + C[m][k - 1];
         T[m] = E[m][W2][0] + E[m][W2][1];
-        base[m] = T[m];
+        base[m - M0] = T[m];
       }
-      if constexpr (M > 1) {
+      if constexpr (M - 1 > M0) {
         if constexpr (SEG)
-          seg_incl_scan_n<LP, ML>(base, segf);
+          seg_incl_scan_n<LP, NSC>(base, segf);
         else
-          group_incl_scan_n<LP, ML>(base);
+          group_incl_scan_n<LP, NSC>(base);
       }
       if constexpr (LP == 64 && M > 1) {
         if (nblk > 1) {  // wave-uniform: carry in from the blocks to the left, carry out to the right
@@ -208,16 +223,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP
       }
       // descending m: level m reads C_m (through E) before level m-1's update writes it
 #pragma unroll
-      for (int m = M - 2; m >= 0; --m) {
+      for (int m = M - 2; m >= M0; --m) {
         f2 off;
-        off[0] = base[m] - T[m];
+        off[0] = base[m - M0] - T[m];
         off[1] = off[0] + E[m][W2][0];
         C[m + 1][0] = fma2(dM[0], off, C[m + 1][0]);
 #pragma unroll
         for (int k = 1; k < W2; ++k) C[m + 1][k] = fma2(dM[k], E[m][k] + off, C[m + 1][k]);
       }
+      if constexpr (U1 && M > 1) {
+        // u_i0 of the group's first lane: a DPP row broadcast where the group is a DPP row, else through the
+        // LDS crossbar
+        float u0;
+        if constexpr (LP == 16)
+          u0 = dpp_f<0x150>(seed.u[0][0]);  // row_newbcast:0
+        else
+          u0 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bc0, __builtin_bit_cast(int, seed.u[0][0])));
 #pragma unroll
-      for (int w2 = 0; w2 < W2; ++w2) C[0][w2] += dM[w2];
+        for (int k = 0; k < W2; ++k) C[1][k] = fma2(dM[k], seed.u[k] - splat2(u0), C[1][k]);
+      }
+      if constexpr (U1) seed.step_u();
+      if constexpr (!U1 || SAVE) {
+#pragma unroll
+        for (int w2 = 0; w2 < W2; ++w2) C[0][w2] += dM[w2];
+      }
     };
     auto do_row = [&](auto clo_t, int i, const Rec &rd, bool anch, const f2 *pc = nullptr) {
       f2 dM[W2];
@@ -308,8 +337,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP
         }
       } else {
       if constexpr (PK && !MF && SPLIT != 2) {
-        // Runs of hot rows (RbfSeedPk::row_hot: no exact evaluation in the body, so kc, Eq and kcR are
-        // advanced in their registers), each ended by the row that needs the exact path: the anchor row, or
+        // Runs of hot rows (RbfSeedPk::hot_dots, hot_cells: no exact evaluation in the body, so kc, Eq and u
+        // are advanced in their registers), each ended by the row that needs the exact path: the anchor row, or
         // a row with a cell outside the polynomial range, which leaves the run before any state is written
         // and is evaluated again, whole, by row().  The record of row i + 1 (clamped to the last row) is
         // loaded before row i's arithmetic, so its scalar-cache latency is not waited for, and that row's
@@ -337,9 +366,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fo_waves(DP
           bool slow = false;
           for (; i < stop; ++i) {
             nxt.load(fx, min(i + 1, nrows - 1));
-            f2 dM[W2];
-            slow = seed.template row_hot<CLO>(cur, p0, dM);
+            f2 c[W2], dM[W2];
+            slow = seed.template hot_dots<CLO>(cur, p0, c);
             if (slow) break;
+            seed.template hot_cells<CLO>(p0, c, dM);
             levels(i, dM);
             p0 = seed.p0_dot(nxt);
             cur.set(nxt);
