@@ -96,6 +96,19 @@ int wide_diag_tiles(const float *FX, long long sx, int d, int lw, int a0, int np
 bool ho_bwd_supported(int l2, int order, int M, int seed);
 size_t ho_bwd_slab_bytes(int l2, int order, int M);
 int sig_ho_bwd_launch(const BwdArgs &a, int order, int seed, long long nblocks, hipStream_t s);
+// gpsig_sig_vjp_ho_route: the plan sig_ho_bwd_launch follows (ho_bwd_plan, sig_ho_bwd_split.h), the slab region
+// of the workspace, and the row chunks and kernel launches of sig_bwd_wide (include/gpsig_amd.h for the values)
+struct HoVjpRoute {
+  int kernel, W, waves, slots, variant, chunks, launches;
+  size_t lds_bytes, slab_bytes;
+};
+bool sig_ho_bwd_route_plan(int l2, int order, int M, HoVjpRoute *r);  // false: no kernel covers the shape
+// launches of one chunk of sig_bwd_wide: rows [row_begin, row_end), nblocks pair tiles
+int sig_ho_bwd_route_launches(int l2, int order, int M, int pair_mode, int row_begin, int row_end, int n2,
+                              long long nblocks, int *launches);
+// sig_bwd_wide.hip: r->chunks and r->launches of a call over rows [row_begin, row_end), and its return code
+int sig_bwd_wide_ho_route(int n1, int l1, int n2, int l2, int d, int M, int order, int seed, int pair_mode,
+                          int row_begin, int row_end, HoVjpRoute *r);
 
 // ---- sig_tens.hip / sig_tvs_pk.hip: tensors against sequences
 size_t tvs_features_bytes(int n, int l, int d);

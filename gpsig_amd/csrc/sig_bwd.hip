@@ -249,6 +249,37 @@ extern "C" int gpsig_sig_gram_vjp_ho(const float *X, int n1, int l1, const float
                  reinterpret_cast<hipStream_t>(stream));
 }
 
+// gpsig_sig_vjp_ho_route: gpsig_sig_gram_vjp_ho's checks in its order, then the plan its launches follow
+// (sig_ho_bwd.hip), the slab region of vjp_plan and the chunk loop of sig_bwd_wide; no launch, no device
+extern "C" int gpsig_sig_vjp_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
+                                      int pair_mode, int row_begin, int row_end, int *out) {
+  if (!out || num_levels < 2 || order < 2) return GPSIG_EINVAL;
+  // the query has no inputs: out stands in for the pointers the shared check wants present
+  if (check_pair_args(out, out, n1, l1, n2, l2, d, 2, pair_mode, row_begin, row_end, false)) return GPSIG_EINVAL;
+  for (int i = 0; i < GPSIG_SIG_VJP_HO_ROUTE_INTS; ++i) out[i] = 0;
+  const int seed = vjp_seed(base_kind, true);
+  HoVjpRoute r{};
+  if (seed < 0 || !ho_bwd_supported(l2, order, num_levels, seed)) return GPSIG_EUNSUPPORTED;
+  sig_ho_bwd_route_plan(l2, order, num_levels, &r);
+  VjpPlan pl;
+  if (!vjp_plan(n1, l1, n2, l2, d, num_levels, order, seed, true, pair_mode != GPSIG_PAIRS_RECT, &pl))
+    return GPSIG_EUNSUPPORTED;
+  r.slab_bytes = pl.slab;
+  // no rows: vjp_run returns before the chunk loop, so the geometry alone
+  const int rc = row_end == row_begin ? GPSIG_OK : sig_bwd_wide_ho_route(n1, l1, n2, l2, d, num_levels, order, seed,
+                                                                         pair_mode, row_begin, row_end, &r);
+  out[0] = r.kernel;
+  out[1] = r.W;
+  out[2] = r.waves;
+  out[3] = r.slots;
+  out[4] = r.variant;
+  out[5] = (int)r.lds_bytes;
+  out[6] = r.slab_bytes > 0x7fffffff ? 0x7fffffff : (int)r.slab_bytes;
+  out[7] = r.chunks;
+  out[8] = r.launches;
+  return rc;
+}
+
 extern "C" size_t gpsig_sig_vjp_ho_workspace_bytes(int n1, int l1, int n2, int l2, int d, int num_levels, int order,
                                                    int base_kind) {
   if (n1 <= 0 || n2 <= 0 || l1 < 2 || l2 < 2 || d <= 0 || order < 1) return 0;

@@ -168,6 +168,44 @@ size_t sig_bwd_wide_workspace(int n1, int l1, int n2, int l2, int d) {
   return best;
 }
 
+// The row chunks of a call over rows [rb0, rb1), `rows` x-rows each: f(r0, r1, c0) per chunk -- tile rows from
+// the 4-aligned r0, the chunk's own rows [c0, r1) -- until one returns nonzero
+template <class F>
+static int wide_for_chunks(int rb0, int rb1, int rows, F &&f) {
+  for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += rows) {
+    const int r1 = r0 + rows < rb1 ? r0 + rows : rb1;
+    const int c0 = r0 > rb0 ? r0 : rb0;
+    const int rc = f(r0, r1, c0);
+    if (rc) return rc;
+  }
+  return GPSIG_OK;
+}
+// pair tiles of one chunk: from the chunk's first 4-aligned row r0 (DIAG: its pairs from c0)
+static int wide_chunk_tiles(int pm, int r0, int r1, int c0, int n2, int G, PairTiles *pt) {
+  return pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, G, pt);
+}
+// pairs per wave of the higher-order VJP's tiles (one: BwdGeo{4, 64})
+constexpr int HO_BWD_W = 4, HO_BWD_LP = 64;
+
+// gpsig_sig_vjp_ho_route: the chunks of sig_bwd_wide at order > 1 and the launches sig_ho_bwd_launch issues in
+// each, by the same chunk loop, tile counts and plan; no launch
+int sig_bwd_wide_ho_route(int n1, int l1, int n2, int l2, int d, int M, int order, int seed, int pair_mode,
+                          int row_begin, int row_end, HoVjpRoute *r) {
+  r->chunks = r->launches = 0;
+  if (!ho_bwd_supported(l2, order, M, seed)) return GPSIG_EUNSUPPORTED;
+  const WidePlan pl = wide_plan(n1, l1, n2, l2, d, pair_mode);
+  return wide_for_chunks(row_begin, row_end, pl.rows, [&](int r0, int r1, int c0) -> int {
+    PairTiles pt;
+    int rc = wide_chunk_tiles(pair_mode, r0, r1, c0, n2, 64 / HO_BWD_LP, &pt), launches = 0;
+    ++r->chunks;
+    if (rc) return rc;
+    if (pt.nblocks > 0 && (rc = sig_ho_bwd_route_launches(l2, order, M, pair_mode, c0, r1, n2, pt.nblocks, &launches)))
+      return rc;
+    r->launches += launches;
+    return GPSIG_OK;
+  });
+}
+
 // The wide-channel VJP (order 1) and the higher-order VJP (order > 1, sig_ho_bwd.h: one pair per wave, the
 // same tiles and GEMMs).  a: filled by the caller as for the fixed kernels (pair mode, rows, gout, rs,
 // scale, jitter, gX/gY/grs, gscale slots, state); X, Y the raw (n, l, d) inputs.
@@ -175,7 +213,7 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
                  hipStream_t s, int order) {
   const int n1 = a.n1, l1 = a.l1, n2 = a.n2, l2 = a.l2, d = a.d, pm = a.pair_mode;
   if (order > 1 ? !ho_bwd_supported(l2, order, a.M, seed) || a.state : l2 > 512) return GPSIG_EUNSUPPORTED;
-  const BwdGeo geo = order > 1 ? BwdGeo{4, 64} : bwd_geometry_wide(l2);
+  const BwdGeo geo = order > 1 ? BwdGeo{HO_BWD_W, HO_BWD_LP} : bwd_geometry_wide(l2);
   const WidePlan pl = wide_plan(n1, l1, n2, l2, d, pm);
   if (!workspace || workspace_bytes < plan_bytes(pl)) return GPSIG_EWORKSPACE;
   char *w = static_cast<char *>(workspace);
@@ -212,18 +250,15 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
   const int G = 64 / geo.LP;
   const int rb0 = a.row_begin, rb1 = a.row_end;
   const bool rbf = seed == SEED_RBF_DIFF || seed == SEED_RBF_POINT;
-  for (int r0 = (rb0 / 4) * 4; r0 < rb1; r0 += pl.rows) {
-    const int r1 = r0 + pl.rows < rb1 ? r0 + pl.rows : rb1;
-    const int c0 = r0 > rb0 ? r0 : rb0;  // rows of this chunk: [c0, r1)
-    const int nr = r1 - r0;              // tile rows from r0 (the chunk's first 4-aligned row)
+  rc = wide_for_chunks(rb0, rb1, pl.rows, [&](int r0, int r1, int c0) -> int {
+    const int nr = r1 - r0;  // tile rows from r0 (the chunk's first 4-aligned row); the chunk's rows: [c0, r1)
     BwdArgs c = a;
     c.row_begin = c0;
     c.row_end = r1;
     c.blk0 = 0;
     c.tile_a0 = r0;
-    // tiles from the chunk's first 4-aligned row r0 (DIAG: its pairs from c0)
     PairTiles pt;
-    const int trc = pair_tiles(pm, pm == GPSIG_PAIRS_DIAG ? c0 : r0, r1, n2, G, &pt);
+    const int trc = wide_chunk_tiles(pm, r0, r1, c0, n2, G, &pt);
     const long long nblocks = pt.nblocks;
     long long tcols;  // tile row length (floats)
     if (pm == GPSIG_PAIRS_DIAG) {
@@ -295,7 +330,9 @@ int sig_bwd_wide(BwdArgs a, const float *X, const float *Y, int seed, void *work
                          0, 1.0f, Gc + (long long)c.tile_b0 * l2 * D1, D1, 0, 1, 0, 0, part, pl.part)))
         return rc;
     }
-  }
+    return GPSIG_OK;
+  });
+  if (rc) return rc;
   // point gradients: rows [rb0, rb1) of x from Gx; all of y (or x again) from Gc
   {
     const long long r0 = (long long)rb0 * l1, nrw = (long long)(rb1 - rb0) * l1;

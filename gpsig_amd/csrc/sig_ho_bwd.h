@@ -61,6 +61,22 @@ struct HoBwdLayout {
   static constexpr int np = po(M + 1);
 };
 
+// HoBwdLayout<o, M>::np and ::ncb for a runtime effective order o = min(order, M): with d_k = min(k, o) blocks
+// per side at level k, the multipliers P_k[x][y] of levels 2..M and the column sums CB_k[y] of levels 1..M.
+// Their sum is the slab slots of one pair in the LDS-state and split kernels (the launch templates assert that
+// it equals the layout's); the host's support checks, workspace sizes and route query all count with these.
+constexpr int ho_bwd_np(int o, int M) {
+  int n = 0;
+  for (int k = 2; k <= M; ++k) n += (k < o ? k : o) * (k < o ? k : o);
+  return n;
+}
+constexpr int ho_bwd_ncb(int o, int M) {
+  int n = 0;
+  for (int k = 1; k <= M; ++k) n += k < o ? k : o;
+  return n;
+}
+constexpr int ho_bwd_slots(int o, int M) { return ho_bwd_np(o, M) + ho_bwd_ncb(o, M); }
+
 // LDS of the multipliers P of one 4-wave workgroup (W = 4 columns per lane)
 template <int ORD, int M>
 constexpr size_t ho_bwd_lds_bytes() {

@@ -24,8 +24,16 @@
 #ifndef HO_LDS_NOFENCE_SLOTS
 #define HO_LDS_NOFENCE_SLOTS 100  // 99 slots (order 5 at 6 levels, 4 at 7) run unfenced without spills; 111 (order 6) spill
 #endif
+// slab slots up to which the W = 4 kernel also leaves its accumulations unpinned (PIN below)
+#define HO_LDS_NOPIN_SLOTS 60
 
 namespace gpsig {
+
+// The three code variants of sig_ho_bwd_lds_kernel by columns per lane and slab slots (FENCE and PIN in the
+// kernel; the route query reports them as variant 2, 1 and 0): fenced at W = 8 and past HO_LDS_NOFENCE_SLOTS,
+// pinned past HO_LDS_NOPIN_SLOTS, neither below
+constexpr bool ho_lds_fenced(int W, int slots) { return W > 4 || slots > HO_LDS_NOFENCE_SLOTS; }
+constexpr bool ho_lds_pinned(int W, int slots) { return ho_lds_fenced(W, slots) || slots > HO_LDS_NOPIN_SLOTS; }
 
 template <int ORD, int M>
 constexpr int ho_lds_np() { return HoBwdLayout<ORD, M>::np; }
@@ -130,10 +138,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) void si
   // Compiler barriers around the slab accesses bound the register use where the slab is large (W = 8, or many
   // slots): without them a level's reads are hoisted and the kernel spills (W = 4 at 7 levels).  Small slabs
   // go without: the reads of a level batch ahead of their use (each lane touches only its own columns).
-  constexpr bool FENCE = W > 4 || Lay::np + Lay::ncb > HO_LDS_NOFENCE_SLOTS;
+  constexpr bool FENCE = ho_lds_fenced(W, Lay::np + Lay::ncb);
   // an empty volatile statement on v: orders the computation of v with the slab accesses around it (with the
   // barriers, and for slabs past 60 slots; otherwise the accumulation is scheduled freely)
-  constexpr bool PIN = FENCE || Lay::np + Lay::ncb > 60;  // unpinned past 60 slots the W = 4 kernel spills
+  constexpr bool PIN = ho_lds_pinned(W, Lay::np + Lay::ncb);  // unpinned past 60 slots the W = 4 kernel spills
   auto pin = [&](float (&v)[W]) {
     if constexpr (PIN) {
 #pragma unroll
@@ -464,20 +472,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) void si
   pt.norm(K);
 }
 
-// one translation unit per effective order (sig_ho_bwd_lds_inst.hip)
-template <int ORD>
-int sig_ho_bwd_lds_launch_o(const BwdArgs &a, int seed, long long nblocks, hipStream_t s);
-
-// (effective order, levels, points) the LDS kernel covers: the multiplier slab of W = 4 / 8 columns fits
+// (effective order, levels) the LDS kernel covers at W = 4 (l2 <= 256) / 8 (l2 <= 512) columns per lane: the
+// slab and the cell buffer fit the LDS
 constexpr int HO_LDS_MAX_ORD = 6;  // order 6: 6 levels at up to 256 points (W = 4: 111 slab slots, 122 KB)
-inline bool ho_bwd_lds_fits(int o, int M, int l2) {
-  int np = 0;
-  for (int k = 1; k <= M; ++k) {
-    const int d = k < o ? k : o;
-    np += (k >= 2 ? d * d : 0) + d;  // multipliers of levels 2..M, column sums of levels 1..M
-  }
-  const int W = l2 <= 256 ? 4 : 8;
-  return (size_t)np * 64 * W * sizeof(float) + ho_bwd_lds_cbuf_bytes(W) <= 160 * 1024;
+constexpr size_t HO_BWD_LDS_BUDGET = 160 * 1024;
+constexpr bool ho_bwd_lds_ok(int o, int M, int W) {
+  return o <= HO_LDS_MAX_ORD &&
+         (size_t)ho_bwd_slots(o, M) * 64 * W * sizeof(float) + ho_bwd_lds_cbuf_bytes(W) <= HO_BWD_LDS_BUDGET;
 }
 
 }  // namespace gpsig

@@ -10,20 +10,24 @@
 
 namespace gpsig {
 
+// The plan (ho_bwd_plan, sig_ho_bwd_split.h) decides which of these runs; each asserts the plan's condition for
+// its (order, levels), so a kernel whose state does not fit is never instantiated, and that its slab has the
+// slots the plan counts.
+template <int ORD, int M>
+constexpr bool ho_slots_match() { return ho_bwd_slots(ORD, M) == HoBwdLayout<ORD, M>::np + HoBwdLayout<ORD, M>::ncb; }
+
 template <int ORD, int M, int W>
 static int launch_lds(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
   constexpr size_t lds = ho_bwd_lds_slab_bytes<ORD, M, W>();
-  if constexpr (lds + ho_bwd_lds_cbuf_bytes(W) > 160 * 1024) {
+  static_assert(ho_slots_match<ORD, M>(), "slab slots");
+  static_assert(ho_bwd_lds_ok(ORD, M, W) && lds + ho_bwd_lds_cbuf_bytes(W) <= HO_BWD_LDS_BUDGET, "LDS");
+  if (seed == SEED_RBF_DIFF)
+    hipLaunchKernelGGL((sig_ho_bwd_lds_kernel<ORD, M, W, SEED_RBF_DIFF>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
+  else if (seed == SEED_LIN_DIFF)
+    hipLaunchKernelGGL((sig_ho_bwd_lds_kernel<ORD, M, W, SEED_LIN_DIFF>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
+  else
     return GPSIG_EUNSUPPORTED;
-  } else {
-    if (seed == SEED_RBF_DIFF)
-      hipLaunchKernelGGL((sig_ho_bwd_lds_kernel<ORD, M, W, SEED_RBF_DIFF>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-    else if (seed == SEED_LIN_DIFF)
-      hipLaunchKernelGGL((sig_ho_bwd_lds_kernel<ORD, M, W, SEED_LIN_DIFF>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-    else
-      return GPSIG_EUNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
-  }
+  return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
 
 // one pair over the 4 SIMDs of a CU (sig_ho_bwd_split.h): 257..509 points; GPSIG_HO_SPLIT=0 keeps the one-wave
@@ -31,31 +35,28 @@ static int launch_lds(const BwdArgs &a, int seed, long long nblocks, hipStream_t
 template <int ORD, int M>
 static int launch_split(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
   constexpr size_t lds = ho_bwd_split_slab_bytes<ORD, M>();
-  if constexpr (lds + ho_bwd_lds_cbuf_bytes(8) + 2 * HO_SPLIT_NW * HO_SPLIT_XN * 4 > 160 * 1024) {
+  static_assert(ho_slots_match<ORD, M>() && lds == ho_bwd_split4_lds_bytes(ORD, M), "slab slots");
+  static_assert(ho_bwd_split4_ok(ORD, M), "LDS");
+  if (seed == SEED_RBF_DIFF)
+    hipLaunchKernelGGL((sig_ho_bwd_split_kernel<ORD, M, SEED_RBF_DIFF>), dim3((unsigned)nblocks),
+                       dim3(64 * HO_SPLIT_NW), lds, s, a);
+  else if (seed == SEED_LIN_DIFF)
+    hipLaunchKernelGGL((sig_ho_bwd_split_kernel<ORD, M, SEED_LIN_DIFF>), dim3((unsigned)nblocks),
+                       dim3(64 * HO_SPLIT_NW), lds, s, a);
+  else
     return GPSIG_EUNSUPPORTED;
-  } else {
-    if (seed == SEED_RBF_DIFF)
-      hipLaunchKernelGGL((sig_ho_bwd_split_kernel<ORD, M, SEED_RBF_DIFF>), dim3((unsigned)nblocks),
-                         dim3(64 * HO_SPLIT_NW), lds, s, a);
-    else if (seed == SEED_LIN_DIFF)
-      hipLaunchKernelGGL((sig_ho_bwd_split_kernel<ORD, M, SEED_LIN_DIFF>), dim3((unsigned)nblocks),
-                         dim3(64 * HO_SPLIT_NW), lds, s, a);
-    else
-      return GPSIG_EUNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
-  }
+  return hipGetLastError() == hipSuccess ? GPSIG_OK : GPSIG_ELAUNCH;
 }
 
 // 510 .. 1017 points: 8 waves per pair, 2 per SIMD, the slab in the caller's global region (a.scratch), at most
 // HO_SPLIT8_BLOCKS workgroups per launch (each owns scr_stride floats of the region)
 template <int ORD, int M>
-static int launch_split8(BwdArgs a, int seed, long long nblocks, hipStream_t s) {
+static int launch_split8(BwdArgs a, const HoBwdPlan &pl, int seed, long long nblocks, hipStream_t s) {
   constexpr int NW = HO_SPLIT8_NW;
-  if constexpr (!ho_split8_ok(ORD, M)) {
-    return GPSIG_EUNSUPPORTED;
-  } else {
+  static_assert(ho_slots_match<ORD, M>() && ho_split8_ok(ORD, M), "8-wave form");
   if (!a.scratch) return GPSIG_EWORKSPACE;
-  a.scr_stride = ho_split_slab_floats<ORD, M>(NW);
+  static_assert(ho_split_slab_floats_rt(ORD, M, NW) == ho_split_slab_floats<ORD, M>(NW), "slab stride");
+  a.scr_stride = pl.slab_floats;  // the stride the workspace's slab region was sized by
   for (long long b0 = 0; b0 < nblocks; b0 += HO_SPLIT8_BLOCKS) {
     const long long nb = nblocks - b0 < HO_SPLIT8_BLOCKS ? nblocks - b0 : HO_SPLIT8_BLOCKS;
     BwdArgs c = a;
@@ -69,24 +70,33 @@ static int launch_split8(BwdArgs a, int seed, long long nblocks, hipStream_t s) 
     if (hipGetLastError() != hipSuccess) return GPSIG_ELAUNCH;
   }
   return GPSIG_OK;
-  }
 }
 
+// launches what the plan says: a kernel is instantiated exactly where the plan can choose it for (ORD, M)
 template <int ORD, int M>
-static int launch_lds_w(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
-  // 510 .. 512 points at (order, levels) the 8-wave form does not hold keep the one-wave W = 8 kernel
-  if (a.l2 > HO_SPLIT_NW * HO_SPLIT_CPB + 1 && ho_split8_ok(ORD, M)) return launch_split8<ORD, M>(a, seed, nblocks, s);
-  if (a.l2 <= 256) return launch_lds<ORD, M, 4>(a, seed, nblocks, s);
-  if (ho_split_on() && ho_bwd_split_fits(ORD, M, a.l2)) return launch_split<ORD, M>(a, seed, nblocks, s);
-  return launch_lds<ORD, M, 8>(a, seed, nblocks, s);
+static int launch_lds_w(const BwdArgs &a, const HoBwdPlan &pl, int seed, long long nblocks, hipStream_t s) {
+  if constexpr (ho_split8_ok(ORD, M)) {
+    if (pl.kernel == HO_BWD_SPLIT8) return launch_split8<ORD, M>(a, pl, seed, nblocks, s);
+  }
+  if constexpr (ho_bwd_lds_ok(ORD, M, 4)) {
+    if (pl.kernel == HO_BWD_LDS && pl.W == 4) return launch_lds<ORD, M, 4>(a, seed, nblocks, s);
+  }
+  if constexpr (ho_bwd_split4_ok(ORD, M)) {
+    if (pl.kernel == HO_BWD_SPLIT4) return launch_split<ORD, M>(a, seed, nblocks, s);
+  }
+  if constexpr (ho_bwd_lds_ok(ORD, M, 8)) {
+    if (pl.kernel == HO_BWD_LDS && pl.W == 8) return launch_lds<ORD, M, 8>(a, seed, nblocks, s);
+  }
+  return GPSIG_EUNSUPPORTED;
 }
 
 template <>
-int sig_ho_bwd_lds_launch_o<GPSIG_ORD>(const BwdArgs &a, int seed, long long nblocks, hipStream_t s) {
+int sig_ho_bwd_lds_launch_o<GPSIG_ORD>(const BwdArgs &a, const HoBwdPlan &pl, int seed, long long nblocks,
+                                       hipStream_t s) {
   constexpr int O = GPSIG_ORD;
   return dispatch<2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto lv) {
     constexpr int M = decltype(lv)::value;
-    if constexpr (M >= O) return launch_lds_w<O, M>(a, seed, nblocks, s); else return (int)GPSIG_EUNSUPPORTED;
+    if constexpr (M >= O) return launch_lds_w<O, M>(a, pl, seed, nblocks, s); else return (int)GPSIG_EUNSUPPORTED;
   });
 }
 

@@ -31,32 +31,82 @@ template <int ORD, int M>
 constexpr long long ho_split_slab_floats(int nw) {
   return (long long)nw * (HoBwdLayout<ORD, M>::np + HoBwdLayout<ORD, M>::ncb) * 64 * HO_SPLIT_W;
 }
-inline long long ho_split_slab_floats_rt(int o, int M, int nw) {
-  int np = 0;
-  for (int k = 1; k <= M; ++k) {
-    const int d = k < o ? k : o;
-    np += (k >= 2 ? d * d : 0) + d;
-  }
-  return (long long)nw * np * 64 * HO_SPLIT_W;
+constexpr long long ho_split_slab_floats_rt(int o, int M, int nw) {
+  return (long long)nw * ho_bwd_slots(o, M) * 64 * HO_SPLIT_W;
 }
+constexpr int HO_SPLIT4_MAX_L = HO_SPLIT_NW * HO_SPLIT_CPB + 1;   // 509 points: 4 blocks of 127 cells
+constexpr int HO_SPLIT8_MAX_L = HO_SPLIT8_NW * HO_SPLIT_CPB + 1;  // 1017 points: 8 blocks
+constexpr long long ho_split8_launches(long long nblocks) { return (nblocks + HO_SPLIT8_BLOCKS - 1) / HO_SPLIT8_BLOCKS; }
 // the 8-wave form covers 510 .. 1017 points where its per-lane state fits 256 VGPRs (2 waves per SIMD) without
 // spilling: levels up to 7 / 6 / 5 / 5 at effective order 2 / 3 / 4 / 5 (order 5 with the RBF seed: 20 bytes)
 constexpr bool ho_split8_ok(int o, int M) { return (o == 2 && M <= 7) || (o == 3 && M <= 6) || ((o == 4 || o == 5) && M <= 5); }
-inline bool ho_bwd_split8_fits(int o, int M, int l2) {
-  return l2 > HO_SPLIT_NW * HO_SPLIT_CPB + 1 && l2 <= HO_SPLIT8_NW * HO_SPLIT_CPB + 1 && ho_split8_ok(o, M);
+
+// (effective order, levels) the 4-wave split kernel covers (257 .. 509 points; wide records padded to 512
+// columns, so every block's 128 columns lie in the record): the slab of 4 x 64 x 2 columns, the cell buffers of
+// the 4 waves and the exchange buffer fit the LDS
+constexpr size_t ho_bwd_split4_lds_bytes(int o, int M) {
+  return (size_t)ho_split_slab_floats_rt(o, M, HO_SPLIT_NW) * sizeof(float);
+}
+constexpr bool ho_bwd_split4_ok(int o, int M) {
+  return o <= HO_LDS_MAX_ORD &&
+         ho_bwd_split4_lds_bytes(o, M) + ho_bwd_lds_cbuf_bytes(8) + 2 * HO_SPLIT_NW * HO_SPLIT_XN * 4 <= HO_BWD_LDS_BUDGET;
+}
+// the register kernel (sig_ho_bwd.h: one pair per wave, 4 per workgroup, l2 <= 256)
+constexpr bool ho_bwd_reg_ok(int o, int M) { return o == 2 || (o == 3 && M <= 5); }
+
+// ---- The plan of one higher-order VJP call: the single decision of which kernel runs a shape.  The support
+// check, the workspace's slab region, the launchers (sig_ho_bwd.hip, sig_ho_bwd_lds_inst.hip) and the route
+// query (gpsig_sig_vjp_ho_route) all read it; the launch templates static_assert its conditions.
+enum { HO_BWD_NONE = -1, HO_BWD_REG = 0, HO_BWD_LDS = 1, HO_BWD_SPLIT4 = 2, HO_BWD_SPLIT8 = 3 };
+struct HoBwdPlan {
+  int kernel;             // HO_BWD_*; HO_BWD_NONE: no kernel covers the shape (GPSIG_EUNSUPPORTED)
+  int W, waves;           // columns per lane, waves per pair
+  int slots;              // multipliers + column sums (ho_bwd_slots)
+  int variant;            // HO_BWD_LDS: 0 unpinned, 1 pinned, 2 fenced (ho_lds_pinned / ho_lds_fenced)
+  size_t lds_bytes;       // dynamic LDS of one workgroup
+  long long slab_floats;  // HO_BWD_SPLIT8: one workgroup's slab in the global region (BwdArgs::scr_stride)
+};
+// o = min(order, M); split_on: ho_split_on() (GPSIG_HO_SPLIT=0 keeps the one-wave W = 8 kernel at 257 .. 509 points)
+constexpr HoBwdPlan ho_bwd_plan(int l2, int o, int M, bool split_on) {
+  HoBwdPlan p{HO_BWD_NONE, 0, 0, 0, 0, 0, 0};
+  if (l2 < 2 || M < 2 || M > 8 || o < 2 || o > M) return p;
+  p.slots = ho_bwd_slots(o, M);
+  auto lds = [&](int W) {
+    p.kernel = HO_BWD_LDS;
+    p.W = W;
+    p.waves = 1;
+    p.variant = ho_lds_fenced(W, p.slots) ? 2 : (ho_lds_pinned(W, p.slots) ? 1 : 0);
+    p.lds_bytes = (size_t)p.slots * 64 * W * sizeof(float);
+  };
+  if (l2 > HO_SPLIT4_MAX_L && l2 <= HO_SPLIT8_MAX_L && ho_split8_ok(o, M)) {
+    p.kernel = HO_BWD_SPLIT8;
+    p.W = HO_SPLIT_W;
+    p.waves = HO_SPLIT8_NW;
+    p.slab_floats = ho_split_slab_floats_rt(o, M, HO_SPLIT8_NW);
+  } else if (l2 > 512) {
+    // past the one-wave kernel's 64 x 8 columns
+  } else if (l2 <= 256 && ho_bwd_reg_ok(o, M)) {
+    p.kernel = HO_BWD_REG;
+    p.W = 4;
+    p.waves = 1;
+    p.lds_bytes = (size_t)4 * ho_bwd_np(o, M) * 64 * 4 * sizeof(float);
+  } else if (l2 <= 256) {
+    if (ho_bwd_lds_ok(o, M, 4)) lds(4);
+  } else if (split_on && l2 <= HO_SPLIT4_MAX_L && ho_bwd_split4_ok(o, M)) {
+    p.kernel = HO_BWD_SPLIT4;
+    p.W = HO_SPLIT_W;
+    p.waves = HO_SPLIT_NW;
+    p.lds_bytes = ho_bwd_split4_lds_bytes(o, M);
+  } else if (ho_bwd_lds_ok(o, M, 8)) {
+    lds(8);
+  }
+  return p;
 }
 
-// (effective order, levels, points) the split kernel covers: 257 .. 4 x 127 + 1 points (wide records padded
-// to 512 columns, so every block's 128 columns lie in the record) and the slab of W = 8 fits
-inline bool ho_bwd_split_fits(int o, int M, int l2) {
-  int np = 0;
-  for (int k = 1; k <= M; ++k) {
-    const int d = k < o ? k : o;
-    np += (k >= 2 ? d * d : 0) + d;
-  }
-  const size_t lds = (size_t)np * 64 * 8 * sizeof(float) + ho_bwd_lds_cbuf_bytes(8) + 2 * HO_SPLIT_NW * HO_SPLIT_XN * 4;
-  return l2 > 256 && l2 <= HO_SPLIT_NW * HO_SPLIT_CPB + 1 && lds <= 160 * 1024;
-}
+// one translation unit per effective order (sig_ho_bwd_lds_inst.hip): the LDS-state and split kernels of pl
+template <int ORD>
+int sig_ho_bwd_lds_launch_o(const BwdArgs &a, const HoBwdPlan &pl, int seed, long long nblocks, hipStream_t s);
+
 template <int ORD, int M>
 constexpr size_t ho_bwd_split_slab_bytes() {
   return (size_t)HO_SPLIT_NW * (ho_lds_np<ORD, M>() + HoBwdLayout<ORD, M>::ncb) * 64 * HO_SPLIT_W * sizeof(float);

@@ -335,6 +335,29 @@ def ho_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_level
     return r
 
 
+HO_VJP_KERNELS = ("REG", "LDS", "SPLIT4", "SPLIT8")
+
+
+def ho_vjp_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_levels: int, order: int, base="rbf",
+                 diag: bool = False, rows: tuple | None = None) -> dict:
+    """What sig_gram_vjp at order >= 2 would run for a shape (gpsig_sig_vjp_ho_route: host only, no launch, no
+    device).  n2 None: the symmetric K(X) (diag=True: the diagonal).  kernel (one of HO_VJP_KERNELS), W, waves,
+    slots, variant, lds_bytes, slab_bytes, chunks, launches as include/gpsig_amd.h describes them.  Raises
+    GpsigError where the call would (shapes no kernel covers, base kernels without a VJP)."""
+    import ctypes
+    sym = n2 is None
+    pm = L.PAIRS_DIAG if diag else (L.PAIRS_UPPER if sym else L.PAIRS_RECT)
+    if sym:
+        n2, l2 = n1, l1
+    r0, r1 = (0, n1) if rows is None else rows
+    out = (ctypes.c_int * 9)()
+    rc = L.load().gpsig_sig_vjp_ho_route(n1, l1, n2, l2, d, num_levels, order, base_kind(base), pm, r0, r1, out)
+    L.check(rc, "gpsig_sig_vjp_ho_route")
+    r = dict(zip(("kernel", "W", "waves", "slots", "variant", "lds_bytes", "slab_bytes", "chunks", "launches"), out))
+    r["kernel"] = HO_VJP_KERNELS[r["kernel"]]
+    return r
+
+
 def sig_state_numel(n1: int, n2: int | None, l2: int, num_levels: int) -> int:
     """float32 elements of the saved VJP state of a Gram call (n2 None: symmetric K(X), upper
     triangle)."""

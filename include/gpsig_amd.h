@@ -167,7 +167,15 @@ int gpsig_sig_gram_vjp(const float *X, int n1, int l1, const float *Y, int n2, i
  * min(order, num_levels) <= 6 where the row state fits the LDS (l2 <= 256: order 2-4 to 8 levels,
  * order 5 to 7, order 6 at 6; l2 <= 512: order 2 to 8 levels, 3 to 7, 4 to 5, 5 at 5), and 510 <= l2 <= 1017
  * at order 2 to 7 levels, 3 to 6, 4 and 5 to 5 (8 waves per pair, the multiplier slabs in the workspace: the
- * workspace query includes them); otherwise GPSIG_EUNSUPPORTED, and the workspace query returns 0. */
+ * workspace query includes them); otherwise GPSIG_EUNSUPPORTED, and the workspace query returns 0.  Only l2
+ * is bounded: l1 (RECT) is the number of streamed rows, of any length the workspace holds.
+ *   Epilogue, per level m (level 0 is K_0 = 1) and for gout_levels = 0 summed over m:
+ *     out_m(a, b) = scale_m rs1_m(a) rs2_m(b) (K_m(a, b) + jitter [a == b, GPSIG_PAIRS_UPPER]).
+ *   jitter enters the diagonal pairs of GPSIG_PAIRS_UPPER only (RECT and DIAG ignore it).  rs1, rs2 and scale
+ *   are independent inputs (the call does not differentiate rs through the diagonal).  UPPER evaluates each
+ *   pair a <= b once with the weight gout(a, b) + gout(b, a) (a < b) of the full symmetric matrix; pass rs2 ==
+ *   rs1 there: both sides' dLoss/drs are added to grs1 (grs2 is not used), so grs1 is the gradient of
+ *   Loss = sum_ab gout(a, b) out(a, b) over all n1 x n1 entries.  DIAG writes neither grs nor gscale. */
 size_t gpsig_sig_vjp_ho_workspace_bytes(int n1, int l1, int n2, int l2, int d, int num_levels, int order,
                                         int base_kind);
 int gpsig_sig_gram_vjp_ho(const float *X, int n1, int l1, const float *Y, int n2, int l2, int d, int num_levels,
@@ -361,6 +369,35 @@ int gpsig_pde_route(int l1, int l2, int d, int dyadic, int solver, int pair_mode
 #define GPSIG_SIG_HO_ROUTE_INTS 7
 int gpsig_sig_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
                        int difference, int pair_mode, int row_begin, int row_end, int *out);
+
+/* The same for the higher-order Gram VJP (gpsig_sig_gram_vjp_ho at order >= 2 and num_levels >= 2), with the
+ * shape arguments of that call.  The kernel follows from l2, o = min(order, num_levels) and M = num_levels alone.
+ * With slots(o, M) = sum over levels k = 1..M of d_k + (k >= 2 ? d_k^2 : 0), d_k = min(k, o) (the column sums
+ * and the multipliers a pair keeps per column), an LDS budget of 160 KiB and a cell buffer of
+ * cbuf(W) = 4 x 64 x 2 W x 4 bytes (4 rows, 64 lanes, 2 W floats):
+ *   REG     l2 <= 256, o = 2, or o = 3 with M <= 5: one pair per wave in registers, 4 pairs per workgroup;
+ *   LDS     one wave per pair, o <= 6 and slots x 64 x W x 4 + cbuf(W) <= 160 KiB: W = 4 for the other (o, M) at
+ *           l2 <= 256; W = 8 at 257 <= l2 <= 512 where neither split kernel runs;
+ *   SPLIT4  257 <= l2 <= 509, 4 waves per pair, 2 columns per lane: o <= 6 and slots x 64 x 8 x 4 + cbuf(8) + 256
+ *           <= 160 KiB (the same (o, M) as LDS at W = 8); GPSIG_HO_SPLIT=0 in the environment keeps LDS W = 8;
+ *   SPLIT8  510 <= l2 <= 1017, 8 waves per pair with the slabs in the workspace, at most 1024 workgroups per
+ *           launch: o = 2 with M <= 7, o = 3 with M <= 6, o = 4 or 5 with M <= 5 (whatever GPSIG_HO_SPLIT says);
+ *   nothing else: l2 > 1017, l2 > 512 outside SPLIT8's (o, M), M > 8.
+ * out: GPSIG_SIG_VJP_HO_ROUTE_INTS ints:
+ *   out[0] kernel: 0 REG, 1 LDS, 2 SPLIT4, 3 SPLIT8   out[1] W (columns per lane: 4, 4 or 8, 2, 2)
+ *   out[2] waves per pair (1, 1, 4, 8)   out[3] slots(o, M)
+ *   out[4] LDS code variant: 0 unpinned (W = 4, slots <= 60), 1 pinned (W = 4, 61 .. 100 slots), 2 fenced (W = 4
+ *          past 100 slots, and W = 8); 0 for the other kernels
+ *   out[5] bytes of dynamic LDS of one workgroup (REG: the multipliers of 4 pairs; 0 for SPLIT8)
+ *   out[6] bytes of the workspace's slab region (SPLIT8: 1024 workgroups' slabs; clamped to INT_MAX), else 0
+ *   out[7] chunks of x-rows (each its own point-weight tile and GEMMs)   out[8] VJP kernel launches in total
+ *          (one per chunk; SPLIT8: ceil(pairs of the chunk / 1024) per chunk); both 0 for an empty row window
+ * Returns GPSIG_OK; GPSIG_EINVAL for arguments the call rejects and for order < 2 or num_levels < 2 (the call then
+ * runs the first-order VJP); GPSIG_EUNSUPPORTED where the call returns it (out is zero then): the Matern base
+ * kinds and the shapes no kernel above covers. */
+#define GPSIG_SIG_VJP_HO_ROUTE_INTS 9
+int gpsig_sig_vjp_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
+                           int pair_mode, int row_begin, int row_end, int *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Float64 evaluation of the first-order Gram and diagonal (order 1): double inputs, double arithmetic, double

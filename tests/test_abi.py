@@ -201,6 +201,170 @@ def test_sig_ho_route_query_without_gpu(monkeypatch):
     assert route(4, 74, 2, 70, 3, 8, 8, "linear")[-1] is False
 
 
+def _ho_vjp_slots(o, M):
+    """include/gpsig_amd.h: column sums d_k of levels 1..M plus multipliers d_k^2 of levels 2..M, d_k = min(k, o)."""
+    return sum(min(k, o) + (min(k, o) ** 2 if k >= 2 else 0) for k in range(1, M + 1))
+
+
+def _ho_vjp_expected(l2, o, M, split_on):
+    """The route table from the rules of include/gpsig_amd.h (gpsig_sig_vjp_ho_route), not from the library:
+    (kernel, W, waves, slots, variant, lds_bytes, slab_bytes of one call), or None where nothing covers the shape."""
+    budget = 160 * 1024
+    slots = _ho_vjp_slots(o, M)
+
+    def cbuf(W):
+        return 4 * 64 * 2 * W * 4
+
+    def lds_ok(W):
+        return o <= 6 and slots * 64 * W * 4 + cbuf(W) <= budget
+
+    def lds(W):
+        variant = 2 if (W == 8 or slots > 100) else (1 if slots > 60 else 0)
+        return ("LDS", W, 1, slots, variant, slots * 64 * W * 4, 0)
+    split8_ok = (o == 2 and M <= 7) or (o == 3 and M <= 6) or (o in (4, 5) and M <= 5)
+    if l2 < 2 or M > 8:
+        return None
+    if 510 <= l2 <= 1017 and split8_ok:
+        return ("SPLIT8", 2, 8, slots, 0, 0, 1024 * 8 * slots * 64 * 2 * 4)
+    if l2 > 512:
+        return None
+    if l2 <= 256:
+        if o == 2 or (o == 3 and M <= 5):
+            np_ = slots - sum(min(k, o) for k in range(1, M + 1))  # the multipliers alone, 4 pairs x 64 x 4 columns
+            return ("REG", 4, 1, slots, 0, 4 * np_ * 64 * 4 * 4, 0)
+        return lds(4) if lds_ok(4) else None
+    if split_on and l2 <= 509 and o <= 6 and slots * 64 * 8 * 4 + cbuf(8) + 256 <= budget:
+        return ("SPLIT4", 2, 4, slots, 0, 4 * slots * 64 * 2 * 4, 0)
+    return lds(8) if lds_ok(8) else None
+
+
+@pytest.mark.skipif("GPSIG_HO_SPLIT" in os.environ, reason="GPSIG_HO_SPLIT pins the kernel form the query reports")
+def test_sig_vjp_ho_route_query_without_gpu(monkeypatch):
+    """gpsig_sig_vjp_ho_route is host only: what gpsig_sig_gram_vjp_ho would run for a shape.  Argument errors,
+    the whole support table 2 <= o <= M <= 8 at every length seam with the split on and off against the header's
+    rules, the slot counts and code variants, chunks and launches, and agreement with the support and workspace
+    queries."""
+    import gpsig_amd
+    import gpsig_amd._lib as L
+    from gpsig_amd import ops
+    lib = L.load()
+    out = (ctypes.c_int * 9)()
+
+    def rc(n1=4, l1=45, n2=2, l2=40, d=3, M=4, order=3, base=L.BASE_RBF, pm=L.PAIRS_RECT, r0=0, r1=4, o=out):
+        return lib.gpsig_sig_vjp_ho_route(n1, l1, n2, l2, d, M, order, base, pm, r0, r1, o)
+    assert rc() == L.GPSIG_OK
+    assert rc(o=None) == L.GPSIG_EINVAL
+    assert rc(order=1) == L.GPSIG_EINVAL                    # the first-order VJP is not this query's
+    assert rc(order=0) == L.GPSIG_EINVAL
+    assert rc(M=1) == L.GPSIG_EINVAL                        # one level runs the first-order VJP too
+    assert rc(l2=1) == L.GPSIG_EINVAL
+    assert rc(l1=1) == L.GPSIG_EINVAL
+    assert rc(d=0) == L.GPSIG_EINVAL
+    assert rc(r1=5) == L.GPSIG_EINVAL                       # row window past n1
+    assert rc(r0=3, r1=2) == L.GPSIG_EINVAL
+    assert rc(r0=-1) == L.GPSIG_EINVAL
+    assert rc(pm=L.PAIRS_UPPER) == L.GPSIG_EINVAL           # UPPER pairs X with itself: equal shapes
+    assert rc(pm=3) == L.GPSIG_EINVAL
+    for base in (L.BASE_MATERN12, L.BASE_MATERN32, L.BASE_MATERN52):
+        assert rc(base=base) == L.GPSIG_EUNSUPPORTED and list(out) == [0] * 9
+        assert lib.gpsig_sig_vjp_ho_workspace_bytes(4, 45, 2, 40, 3, 4, 3, base) == 0
+    assert rc(M=9, order=2) == L.GPSIG_EUNSUPPORTED
+
+    keys = ("kernel", "W", "waves", "slots", "variant", "lds_bytes", "slab_bytes")
+    # slot counts of the issue's variant pins
+    assert [_ho_vjp_slots(2, M) for M in range(2, 9)] == [6 * M - 5 for M in range(2, 9)]
+    assert [_ho_vjp_slots(3, M) for M in range(3, 9)] == [19, 31, 43, 55, 67, 79]
+    assert [_ho_vjp_slots(4, M) for M in range(4, 9)] == [39, 59, 79, 99, 119]
+    assert [_ho_vjp_slots(5, M) for M in range(5, 8)] == [69, 99, 129]
+    assert _ho_vjp_slots(6, 6) == 111
+    table = {}
+    for split_on in (True, False):
+        if not split_on:
+            monkeypatch.setenv("GPSIG_HO_SPLIT", "0")
+        for M in range(2, 9):
+            for o in range(2, M + 1):
+                for l2 in (2, 256, 257, 509, 510, 512, 513, 1017, 1018):
+                    exp = _ho_vjp_expected(l2, o, M, split_on)
+                    for base in ("rbf", "linear"):
+                        # order past the level count is the exact kernel: min(order, M)
+                        for order in ((o,) if o < M else (o, o + 3)):
+                            code = lib.gpsig_sig_vjp_ho_route(1, 7, 2, l2, 3, M, order, ops.base_kind(base),
+                                                              L.PAIRS_RECT, 0, 1, out)
+                            what = (split_on, l2, o, M, base, order)
+                            if exp is None:
+                                assert code == L.GPSIG_EUNSUPPORTED, what
+                                assert list(out) == [0] * 9, what
+                                with pytest.raises(gpsig_amd.GpsigError):
+                                    ops.ho_vjp_route(1, 7, 2, l2, 3, M, order, base)
+                            else:
+                                assert code == L.GPSIG_OK, what
+                                r = ops.ho_vjp_route(1, 7, 2, l2, 3, M, order, base)
+                                assert tuple(r[k] for k in keys) == exp, what
+                                assert (r["chunks"], r["launches"]) == (1, 1), what
+                            assert ops.ho_vjp_supported(l2, M, order, base) == (exp is not None), what
+                            ws = lib.gpsig_sig_vjp_ho_workspace_bytes(1, 7, 2, l2, 3, M, order, ops.base_kind(base))
+                            assert (ws > 0) == (exp is not None), what
+                    table[(split_on, l2, o, M)] = None if exp is None else exp[0] + (str(exp[1]) if exp[0] == "LDS" else "")
+        monkeypatch.delenv("GPSIG_HO_SPLIT", raising=False)
+
+    # the orientation table of the split-on routes, spelled out
+    def where(l2, name, split_on=True):
+        return sorted((o, M) for (s, l, o, M), k in table.items() if s == split_on and l == l2 and k == name)
+
+    def pairs(spec):
+        return sorted((o, M) for o, Ms in spec.items() for M in Ms)
+    for l2 in (2, 256):
+        assert where(l2, "REG") == pairs({2: range(2, 9), 3: range(3, 6)})
+        assert where(l2, "LDS4") == pairs({3: (6, 7, 8), 4: range(4, 9), 5: (5, 6, 7), 6: (6,)})
+    for l2 in (257, 509):
+        assert where(l2, "SPLIT4") == pairs({2: range(2, 9), 3: range(3, 8), 4: (4, 5), 5: (5,)})
+        assert where(l2, "LDS8") == [] and where(l2, "SPLIT8") == []
+        assert where(l2, "LDS8", False) == where(l2, "SPLIT4") and where(l2, "SPLIT4", False) == []
+    split8 = pairs({2: range(2, 8), 3: range(3, 7), 4: (4, 5), 5: (5,)})
+    for l2 in (510, 512):
+        for s in (True, False):  # the 8-wave form does not depend on the switch
+            assert where(l2, "SPLIT8", s) == split8
+            assert where(l2, "LDS8", s) == [(2, 8), (3, 7)]
+    for l2 in (513, 1017):
+        assert where(l2, "SPLIT8") == split8
+        assert [k for (s, l, o, M), k in table.items() if l == l2 and k not in (None, "SPLIT8")] == []
+    assert all(k is None for (s, l, o, M), k in table.items() if l == 1018)
+    # every code variant of the W = 4 LDS kernel: unpinned to 60 slots, pinned to 100, fenced past
+    variants = {(o, M): ops.ho_vjp_route(1, 7, 2, 256, 3, M, o)["variant"] for (o, M) in where(256, "LDS4")}
+    assert variants == {(3, 6): 0, (4, 4): 0, (4, 5): 0, (3, 7): 1, (3, 8): 1, (4, 6): 1, (5, 5): 1, (5, 6): 1,
+                        (4, 7): 1, (6, 6): 2, (4, 8): 2, (5, 7): 2}
+
+    # chunks, launches, row windows: l2 decides the kernel, the pair mode and rows the grid
+    def route(*a, **kw):
+        r = ops.ho_vjp_route(*a, **kw)
+        return r["kernel"], r["chunks"], r["launches"]
+    assert route(7, 10, 3, 10, 2, 3, 2, rows=(3, 5)) == ("REG", 1, 1)
+    assert route(7, 10, 3, 10, 2, 3, 2, rows=(2, 2)) == ("REG", 0, 0)        # an empty window: the geometry alone
+    assert route(7, 10, None, None, 2, 4, 4, "linear", rows=(5, 7)) == ("LDS", 1, 1)
+    assert route(7, 10, None, None, 2, 4, 4, diag=True) == ("LDS", 1, 1)
+    assert route(2, 700, 2, 20, 2, 3, 2) == ("REG", 1, 1)                    # l1 does not enter
+    assert route(2, 20, 2, 700, 2, 3, 2) == ("SPLIT8", 1, 1)
+    # the 1 GiB point-weight tile holds 44 rows of 64 sequences of 300 points: two chunks
+    assert route(64, 300, None, None, 3, 4, 3) == ("SPLIT4", 2, 2)
+    # SPLIT8 launches at most 1024 workgroups: the 33 x 33 = 1089 pairs of one chunk go in two, 32 x 32 in one
+    r = ops.ho_vjp_route(33, 12, 33, 510, 2, 2, 2, "linear")
+    assert (r["kernel"], r["chunks"], r["launches"], r["slab_bytes"]) == ("SPLIT8", 1, 2, 1024 * 8 * 7 * 128 * 4)
+    assert route(32, 12, 32, 510, 2, 2, 2, "linear") == ("SPLIT8", 1, 1)
+    assert route(65, 12, 32, 510, 2, 2, 2, "linear") == ("SPLIT8", 1, 3)     # 2080 pairs
+    # 510 rows per x-sequence: the 1 GiB tile holds 28 of them against 33 x 510 columns, 32 against 32 x 510
+    assert route(33, 510, 33, 510, 2, 2, 2, "linear") == ("SPLIT8", 2, 2)
+    assert route(32, 510, 32, 510, 2, 2, 2, "linear") == ("SPLIT8", 1, 1)
+    assert route(33, 510, None, None, 2, 2, 2) == ("SPLIT8", 2, 2)           # 546 + 15 upper pairs
+    assert route(33, 510, None, None, 2, 2, 2, diag=True) == ("SPLIT8", 1, 1)
+    # the slab region is what the workspace query adds for the 8-wave form
+    w510 = lib.gpsig_sig_vjp_ho_workspace_bytes(2, 510, 2, 510, 2, 5, 5, L.BASE_RBF)
+    monkeypatch.setenv("GPSIG_HO_SPLIT", "0")
+    assert ops.ho_vjp_route(2, 300, 2, 300, 2, 3, 2)["kernel"] == "LDS"
+    monkeypatch.delenv("GPSIG_HO_SPLIT")
+    assert ops.ho_vjp_route(2, 300, 2, 300, 2, 3, 2)["kernel"] == "SPLIT4"
+    assert w510 > ops.ho_vjp_route(2, 510, 2, 510, 2, 5, 5)["slab_bytes"] == 1024 * 8 * 69 * 128 * 4
+
+
 def test_graph_capture_refuses_host_tensors_and_kernel_to():
     """gpsig_amd.graphs.GraphedCall takes device tensors only; kern.to() keeps parameter leaves."""
     import torch

@@ -120,21 +120,36 @@ def _walks(n, l, d, seed):
 @pytest.mark.parametrize("L,D,M,order,base", [
     (12, 3, 3, 2, "rbf"), (30, 4, 5, 2, "linear"), (40, 46, 4, 2, "rbf"), (200, 3, 4, 2, "rbf"),
     (25, 3, 4, 3, "rbf"), (20, 2, 5, 3, "linear"), (18, 3, 3, 3, "linear"), (16, 2, 8, 2, "rbf"),
-    # the LDS-state kernel (csrc/sig_ho_bwd_lds.h): orders 4-5, order 3 past 5 levels, 257-512 points
+    # the LDS-state kernel at W = 4 (csrc/sig_ho_bwd_lds.h): orders 4-5, order 3 past 5 levels, up to 256 points
     (25, 3, 5, 4, "rbf"), (20, 2, 5, 5, "linear"), (22, 3, 6, 3, "rbf"), (16, 2, 7, 5, "rbf"),
-    (19, 4, 4, 4, "linear"), (300, 3, 4, 2, "rbf"), (270, 2, 5, 5, "linear"), (400, 3, 5, 4, "rbf"),
+    (19, 4, 4, 4, "linear"),
     # 257-509 points: one pair over the 4 SIMDs of a CU (csrc/sig_ho_bwd_split.h), 3 and 4 column blocks
+    (300, 3, 4, 2, "rbf"), (270, 2, 5, 5, "linear"), (400, 3, 5, 4, "rbf"),
     (381, 3, 4, 3, "rbf"), (509, 2, 3, 2, "linear"),
     # effective order 6 (6 levels, up to 256 points: the LDS-state kernel at W = 4)
     (20, 3, 6, 6, "rbf"), (18, 2, 6, 7, "rbf"), (200, 2, 6, 6, "linear"),
-    # 510-512 points at levels the 8-wave form does not hold: the one-wave W = 8 kernel
+    # 510-512 points at levels the 8-wave form does not hold: the one-wave W = 8 kernel on K(X) and the diagonal
+    # (511 points); the cross pairs' 508 columns run the 4-wave split
     (511, 2, 7, 3, "linear"),
 ])
 def test_higher_order_vjp_kernel_raw_levels(L, D, M, order, base):
-    """gpsig_sig_gram_vjp_ho (csrc/sig_ho_bwd.h, sig_ho_bwd_lds.h) against fp64 autodiff of
+    """gpsig_sig_gram_vjp_ho (csrc/sig_ho_bwd.h, sig_ho_bwd_lds.h, sig_ho_bwd_split.h) against fp64 autodiff of
     signature_kern_higher_order (signature_algs.py:37-74, restated in oracle/autodiff_ref.py): per-level
     upstream gradients, cross K(X, Y), symmetric K(X) (UPPER pairs) and the diagonal."""
     from gpsig_amd import ops
+    # the kernel of the cross pairs (l2 = L - 3) and of K(X) / the diagonal (l2 = L), W of the LDS kernel
+    o = min(order, M)
+    if L == 511:
+        want = (("SPLIT4", 2), ("LDS", 8))
+    elif L > 256:
+        want = (("SPLIT4", 2),) * 2
+    elif o == 2 or (o == 3 and M <= 5):
+        want = (("REG", 4),) * 2
+    else:
+        want = (("LDS", 4),) * 2
+    rc, rs = ops.ho_vjp_route(3, L, 4, L - 3, D, M, order, base), ops.ho_vjp_route(3, L, None, None, D, M, order, base)
+    rd = ops.ho_vjp_route(3, L, None, None, D, M, order, base, diag=True)
+    assert ((rc["kernel"], rc["W"]), (rs["kernel"], rs["W"])) == want and (rd["kernel"], rd["W"]) == want[1]
     X, Y = _walks(3, L, D, L + order), _walks(4, L - 3, D, L + order + 1)
     G = np.random.default_rng(7).standard_normal((M + 1, 3, 4))
     Gs = np.random.default_rng(8).standard_normal((M + 1, 3, 3))
@@ -206,8 +221,9 @@ def test_higher_order_vjp_unsupported_raises():
 def test_higher_order_long_sequences_gradient(normalization):
     """SignatureLinear(num_levels=5, order=5) at the VOSF trainer's sequence shape (d = 24, L = 500,
     benchmarks/models/train_gpsig_vosf.py:102): K (symmetric and cross) and Kdiag gradients through the
-    LDS-state VJP kernel (W = 8 columns per lane), vs fp64 autodiff of the reference graph, plain
-    norm-relative criterion on the gradient itself.
+    4-wave split of the LDS-state VJP kernel (sig_ho_bwd_split.h; the one-wave W = 8 kernel under
+    GPSIG_HO_SPLIT=0), vs fp64 autodiff of the reference graph, plain norm-relative criterion on the gradient
+    itself.
 
     Normalised, the Gram term and the diagonal term of the gradient cancel ~270x (the normalised kernel is
     scale-invariant in each sequence): autograd.SigGram folds the diagonal terms into the weights of the
@@ -217,6 +233,12 @@ def test_higher_order_long_sequences_gradient(normalization):
     from gpsig_amd import ops
     N, L, D, M = 2, 500, 24, 5
     assert ops.ho_vjp_supported(L, M, M, "linear")
+    import os
+    want = "LDS" if os.environ.get("GPSIG_HO_SPLIT", "")[:1] == "0" else "SPLIT4"
+    # K(X), the folded K(X, X2) over [X; X2] padded to L points, and the diagonal
+    assert ops.ho_vjp_route(N, L, None, None, D, M, M, "linear")["kernel"] == want
+    assert ops.ho_vjp_route(N + 2, L, None, None, D, M, M, "linear")["kernel"] == want
+    assert ops.ho_vjp_route(N, L, None, None, D, M, M, "linear", diag=True)["kernel"] == want
     X, X2 = _walks(N, L, D, 21), _walks(2, L - 20, D, 22)
     k = gpsig_amd.SignatureLinear(L * D, D, M, order=M, normalization=normalization)
     Xt = torch.tensor(X.reshape(N, -1), device=DEV, dtype=torch.float32, requires_grad=True)
@@ -251,9 +273,11 @@ def test_higher_order_long_sequences_gradient(normalization):
 
 @pytest.mark.parametrize("L1,L2,D", [(2, 2, 3), (3, 40, 2), (2, 9, 40)])
 def test_higher_order_vjp_short_sequences(L1, L2, D):
-    """Order-2 VJP with one- and two-increment sequences (the recursion's shortest grids), cross pairs."""
+    """Order-2 VJP with one- and two-increment sequences (the recursion's shortest grids), cross pairs: the
+    register kernel."""
     from gpsig_amd import ops
     M = 3
+    assert ops.ho_vjp_route(2, L1, 3, L2, D, M, 2)["kernel"] == "REG"
     X, Y = _walks(2, L1, D, L1 + L2), _walks(3, L2, D, L1 + L2 + 1)
     G = np.random.default_rng(5).standard_normal((M + 1, 2, 3))
     gX, gY = ops.sig_gram_vjp(torch.tensor(X, device=DEV, dtype=torch.float32),
@@ -269,10 +293,12 @@ def test_higher_order_vjp_short_sequences(L1, L2, D):
                                             (400, "rbf", 4, 4)])
 def test_higher_order_vjp_unit_scale_long(L, base, order, M):
     """The reverse sweep recovers the forward column sums by subtraction, CB_m(i) = CB_m(i+1) - colsum R_m(i),
-    over every row: unit-scale increments (walks of N(0, 1) steps, not 1/sqrt(L d)) at 256 (register kernel)
-    and 400 points (LDS-state kernel), cross pairs, per-level upstream gradients, vs fp64 autodiff."""
+    over every row: unit-scale increments (walks of N(0, 1) steps, not 1/sqrt(L d)) at 256 rows against 249
+    columns (register kernel) and 400 against 393 (the 4-wave split of the LDS-state kernel), cross pairs,
+    per-level upstream gradients, vs fp64 autodiff."""
     from gpsig_amd import ops
     D = 2
+    assert ops.ho_vjp_route(2, L, 2, L - 7, D, M, order, base)["kernel"] == ("REG" if L == 256 else "SPLIT4")
     rng = np.random.default_rng(L + order)
     X = np.cumsum(rng.standard_normal((2, L, D)), 1) * (0.1 if base == "rbf" else 1.0)
     Y = np.cumsum(rng.standard_normal((2, L - 7, D)), 1) * (0.1 if base == "rbf" else 1.0)
@@ -287,11 +313,14 @@ def test_higher_order_vjp_unit_scale_long(L, base, order, M):
 
 
 def test_higher_order_vjp_chunked_upper_vs_rect():
-    """The LDS-state VJP over several chunks of x-rows (N = 64 sequences of 300 points: the point-weight tile
-    budget holds 44 rows per chunk): the symmetric K(X) gradient (UPPER pairs, one workgroup per pair from
+    """The split LDS-state VJP over several chunks of x-rows (N = 64 sequences of 300 points: the point-weight
+    tile budget holds 44 rows per chunk): the symmetric K(X) gradient (UPPER pairs, one workgroup per pair from
     each chunk's row window) equals the cross K(X, Y) one with Y a copy of X, dK/dX + dK/dY (RECT pairs)."""
     from gpsig_amd import ops
     N, L, D, M, order = 64, 300, 3, 4, 3
+    for n2 in (None, N):
+        r = ops.ho_vjp_route(N, L, n2, n2 and L, D, M, order)
+        assert (r["kernel"], r["chunks"], r["launches"]) == ("SPLIT4", 2, 2)
     X = _walks(N, L, D, 90)
     G = np.random.default_rng(91).standard_normal((M + 1, N, N))
     Xt = torch.tensor(X, device=DEV, dtype=torch.float32)
@@ -323,8 +352,16 @@ def test_higher_order_vjp_split_matches_one_wave_kernel(L, M, order, base, monke
                                     order=order)[0])
         return [g.cpu().numpy() for g in out]
 
+    def kernels():
+        return [ops.ho_vjp_route(3, L, 2, L - 7, D, M, order, base)["kernel"],
+                ops.ho_vjp_route(3, L, None, None, D, M, order, base)["kernel"],
+                ops.ho_vjp_route(3, L, None, None, D, M, order, base, diag=True)["kernel"]]
+
+    monkeypatch.delenv("GPSIG_HO_SPLIT", raising=False)
+    assert kernels() == ["SPLIT4"] * 3
     split = grads()
     monkeypatch.setenv("GPSIG_HO_SPLIT", "0")
+    assert kernels() == ["LDS"] * 3
     one = grads()
     for g, r in zip(split, one):
         assert norm_rel_err(g, r) < 2e-6
@@ -335,8 +372,11 @@ def test_higher_order_vjp_split_matches_one_wave_kernel(L, M, order, base, monke
 def test_higher_order_vjp_past_512_points(L, D, M, order, base):
     """510-1017 points: one pair over 8 waves (2 per SIMD), the multiplier slab in a global-memory region of the
     workspace (csrc/sig_ho_bwd_split.h, NW = 8), against fp64 autodiff of signature_kern_higher_order on cross,
-    symmetric and diagonal pairs."""
+    symmetric and diagonal pairs.  At 510 points the cross pairs have 505 columns: the 4-wave split."""
     from gpsig_amd import ops
+    assert ops.ho_vjp_route(2, L, 2, L - 5, D, M, order, base)["kernel"] == ("SPLIT4" if L == 510 else "SPLIT8")
+    assert ops.ho_vjp_route(2, L, None, None, D, M, order, base)["kernel"] == "SPLIT8"
+    assert ops.ho_vjp_route(2, L, None, None, D, M, order, base, diag=True)["kernel"] == "SPLIT8"
     X, Y = _walks(2, L, D, L + order), _walks(2, L - 5, D, L + order + 1)
     G = np.random.default_rng(7).standard_normal((M + 1, 2, 2))
     Gd = np.random.default_rng(9).standard_normal((M + 1, 2))
