@@ -86,6 +86,7 @@ SIGNATURES = {
                                      _P]),
     "gpsig_pde_route": (_I, [_I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "gpsig_sig_ho_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "gpsig_sig_fo_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "gpsig_tens_vs_seq": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "gpsig_tens_gram_workspace_bytes": (_SZ, [_I, _I, _I]),
     "gpsig_tens_gram": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),

@@ -64,6 +64,16 @@ static bool diag_tiled(int n, int l, int d, int order) {
   fo_wide_geo(l, SEED_RBF_DIFF, &W, &LP);
   return (long long)LP * W >= l && diag_tiles_apply(l, d, W, LP, SEED_RBF_DIFF, 1);
 }
+// its tiles at the wide forward's geometry, and *cp = the pairs of one chunk of n
+static DiagTiles diag_tiles_plan(int n, int l, int *cp) {
+  int W, LP;
+  fo_wide_geo(l, SEED_RBF_DIFF, &W, &LP);
+  const DiagTiles dt = diag_tiles_of(l, W, LP);
+  *cp = diag_tile_pairs(dt, n);
+  return dt;
+}
+// chunks of cp pairs over the rows [row_begin, row_end); chunk k covers [row_begin + k cp, ...)
+static int diag_tile_chunks(int row_begin, int row_end, int cp) { return (row_end - row_begin + cp - 1) / cp; }
 
 extern "C" size_t gpsig_sig_split_bytes(int l1, int l2, int d, int num_levels) {
   const int DP = pad_channels(d, 1);
@@ -96,10 +106,9 @@ static bool gram_plan(int n1, int l1, int n2, int l2, int d, int num_levels, int
   p->dm = split ? gpsig_sig_split_bytes(l1, l2, d, num_levels) : 0;
   p->mc = p->mf ? align256(mf_gram_scratch_bytes(l1, l2, d)) : 0;
   if (p->dtiles) {
-    int W, LP;
-    fo_wide_geo(l1, SEED_RBF_DIFF, &W, &LP);
-    const DiagTiles dt = diag_tiles_of(l1, W, LP);
-    p->dt = align256((size_t)diag_tile_pairs(dt, n1) * dt.pair * sizeof(float));
+    int cp;
+    const DiagTiles dt = diag_tiles_plan(n1, l1, &cp);
+    p->dt = align256((size_t)cp * dt.pair * sizeof(float));
   }
   Carver c;
   c.take(p->fx);
@@ -212,23 +221,24 @@ static int sig_gram_impl(const float *X, int n1, int l1, const float *Y, int n2,
 
   if (pl.dtiles) {
     // the diagonal's pairs in chunks: their seed tiles (two batched GEMMs + the anchors), then the launch
-    int gW, gLP;
-    fo_wide_geo(l2, seed, &gW, &gLP);
-    const DiagTiles dt = diag_tiles_of(l1, gW, gLP);
-    const int cp = diag_tile_pairs(dt, n1);
+    int cp;
+    const DiagTiles dt = diag_tiles_plan(n1, l1, &cp);
     float *T = ws_at(workspace, pl.o_dt);
     a.dtile = T;
     a.dt_pair = dt.pair;
     a.dt_rows = dt.rows;
     a.dt_ld = dt.ld;
-    for (int c0 = row_begin; c0 < row_end; c0 += cp) {
-      const int c1 = c0 + cp < row_end ? c0 + cp : row_end;
+    const int nchunks = diag_tile_chunks(row_begin, row_end, cp);
+    for (int k = 0; k < nchunks; ++k) {
+      const int c0 = row_begin + k * cp, c1 = c0 + cp < row_end ? c0 + cp : row_end;
       if ((rc = wide_diag_tiles(FX, a.sx, d, a.lw1, c0, c1 - c0, dt, T, s))) return rc;
       SigArgs c = a;
       c.row_begin = c0;
       c.row_end = c1;
       c.dt_a0 = c0;
-      if ((rc = sig_fo_launch(c, DP, seed, (c1 - c0 + 3) / 4, s))) return rc;
+      PairTiles t;
+      if ((rc = pair_tiles(pair_mode, c0, c1, n2, 1, &t))) return rc;
+      if ((rc = sig_fo_launch(c, DP, seed, t.nblocks, s))) return rc;
     }
     return GPSIG_OK;
   }
@@ -240,6 +250,70 @@ static int sig_gram_impl(const float *X, int n1, int l1, const float *Y, int n2,
   a.ntb = t.ntb;
   a.tile_base = t.tile_base;
   return (order == 1) ? sig_fo_launch(a, DP, seed, t.nblocks, s) : sig_ho_launch(a, DP, seed, t.nblocks, s);
+}
+
+// gpsig_sig_fo_route: the choices of sig_gram_impl at order 1 (gpsig_sig_gram / gpsig_sig_diag, and
+// gpsig_sig_gram_state where state != 0), in its order and by the helpers it calls: gram_plan, then sig_fo_mf's
+// tiles and launches (sig_fo_mf_route), the diagonal's tile chunks (diag_tiles_plan, diag_tile_chunks), or
+// fo_lanes_per_pair, pair_tiles and sig_fo_launch's geometry (sig_fo_route); no launch, no device
+extern "C" int gpsig_sig_fo_route(int n1, int l1, int n2, int l2, int d, int num_levels, int base_kind,
+                                  int difference, int pair_mode, int row_begin, int row_end, int state, int *out) {
+  if (!out || num_levels < 1) return GPSIG_EINVAL;
+  // the query has no inputs: out stands in for the pointers the shared check wants present
+  if (check_pair_args(out, out, n1, l1, n2, l2, d, difference ? 2 : 1, pair_mode, row_begin, row_end, false))
+    return GPSIG_EINVAL;
+  // gpsig_sig_gram_state: difference seeds, RECT / UPPER, a state some pair fills
+  if (state && (!difference || gpsig_sig_state_bytes(n1, n2, l2, num_levels, pair_mode) == 0)) return GPSIG_EINVAL;
+  for (int i = 0; i < GPSIG_SIG_FO_ROUTE_INTS; ++i) out[i] = 0;
+  if (base_kind & (GPSIG_BASE_SEED_MFMA | GPSIG_GRAM_SPLIT)) return GPSIG_EUNSUPPORTED;  // A/B variants: not described
+  const int seed = seed_of(base_kind, difference);
+  GramPlan pl{};
+  const bool planned = gram_plan(n1, l1, n2, l2, d, num_levels, 1, seed, pair_mode, pair_mode != GPSIG_PAIRS_RECT,
+                                 false, state != 0, &pl);
+  if (seed < 0 || !planned) return GPSIG_EUNSUPPORTED;
+  if (state && seed_is_radial(seed)) return GPSIG_EUNSUPPORTED;
+  const bool diag = pair_mode == GPSIG_PAIRS_DIAG;
+  FoRoute r{};
+  int rc = GPSIG_OK, cp = 0, G = 0;
+  if (pl.mf) {
+    rc = sig_fo_mf_route(n2, l1, l2, d, num_levels, seed, pair_mode, row_begin, row_end, &r);
+    r.carry = pl.mc;
+  } else if (pl.dtiles) {
+    diag_tiles_plan(n1, l1, &cp);
+    const int nchunks = diag_tile_chunks(row_begin, row_end, cp);
+    for (int k = 0; k < nchunks && !rc; ++k) {
+      const int c0 = row_begin + k * cp, c1 = c0 + cp < row_end ? c0 + cp : row_end;
+      PairTiles t;
+      if ((rc = pair_tiles(pair_mode, c0, c1, n2, 1, &t))) break;
+      rc = sig_fo_route(l1, l2, pl.DP, num_levels, seed, diag, state != 0, t.nblocks, &r);
+    }
+    if (nchunks == 0) rc = sig_fo_route(l1, l2, pl.DP, num_levels, seed, diag, state != 0, 0, &r);  // the geometry alone
+    G = 64 / r.LP;
+  } else {
+    const int LP = fo_lanes_per_pair(l2, pl.DP, num_levels, false, seed, false);
+    if (LP == 0) return GPSIG_EUNSUPPORTED;
+    G = 64 / LP;
+    PairTiles t{};
+    if (row_end > row_begin && (rc = pair_tiles(pair_mode, row_begin, row_end, n2, G, &t))) return rc;
+    rc = sig_fo_route(l1, l2, pl.DP, num_levels, seed, diag, state != 0, t.nblocks, &r);
+  }
+  auto clampi = [](unsigned long long v) { return v > 0x7fffffffULL ? 0x7fffffff : (int)v; };
+  out[0] = pl.mf ? 2 : (pl.wide ? 1 : 0);
+  out[1] = pl.DP;
+  out[2] = r.W;
+  out[3] = r.LP;
+  out[4] = r.nblk;
+  out[5] = clampi(r.carry);
+  out[6] = pl.mf ? 0 : (diag ? 1 : G);
+  out[7] = r.xb;
+  out[8] = r.nw;
+  out[9] = r.np;
+  out[10] = r.cw;
+  out[11] = pl.dtiles ? 1 : 0;
+  out[12] = cp;
+  out[13] = clampi((unsigned long long)r.workgroups);
+  out[14] = r.launches;
+  return row_end == row_begin ? GPSIG_OK : rc;  // no rows: the entry returns before any launch
 }
 
 // gpsig_sig_ho_route: the choices of sig_gram_impl at order > 1 and of sig_ho_launch / sig_ho_tiled under it,

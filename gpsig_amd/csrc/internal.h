@@ -24,6 +24,16 @@ void fo_wide_geo(int l2, int seed, int *W, int *LP);
 size_t fo_split_bytes(int l1, int l2, int DP, int M);
 template <int DP, int M>
 int sig_fo_launch_dpm(const SigArgs &a, int seed, long long nblocks, hipStream_t s);  // sig_fo_inst.hip
+// gpsig_sig_fo_route: what sig_fo_launch (nblocks workgroups) / sig_fo_mf would choose, and their return
+// (include/gpsig_amd.h for the values; workgroups and launches add up over the calls of one query)
+struct FoRoute {
+  int W, LP, nblk;      // columns per lane, lanes per pair, column blocks
+  int nw, np, cw, xb;   // matrix cores: waves per workgroup, operand parts, floats per carry row, x-sequences per workgroup
+  int launches;         // kernel launches
+  long long workgroups;
+  size_t carry;         // dynamic LDS of a blocked launch's carries (sig_fo_launch)
+};
+int sig_fo_route(int l1, int l2, int DP, int M, int seed, bool diag, bool state, long long nblocks, FoRoute *r);
 
 // ---- sig_f64_inst.hip: the float64 first-order kernels of one level count
 struct F64Args;  // sig_f64.h
@@ -36,6 +46,8 @@ size_t mf_records_bytes(int n, int l, int d);
 bool mf_gram_applies(int d, int l2);
 size_t mf_gram_scratch_bytes(int l1, int l2, int d);
 int sig_fo_mf(const SigArgs &a, int d, int seed, float *scratch, hipStream_t s);
+int sig_fo_mf_route(int n2, int l1, int l2, int d, int M, int seed, int pair_mode, int row_begin, int row_end,
+                    FoRoute *r);
 int sig_fo_mf_cells(const float *FX, int n1, int l1, const float *FY, int n2, int l2, int d, int pair_mode,
                     int row_begin, int row_end, float *dm, int dm_a0, int dm_b0, long long dm_as, long long dm_bs,
                     long long dm_ld, hipStream_t s);

@@ -514,12 +514,16 @@ inline size_t fo_carry_bytes(int l1, bool diff, int M, int nblk) {
 }
 constexpr size_t FO_MAX_CARRY_BYTES = 160 * 1024;
 constexpr int FO_MAX_LEVELS = 8;
+// dynamic LDS of a launch: only the 64-lane geometry runs column blocks
+inline size_t fo_launch_lds(int LP, int l1, bool diff, int M, int nblk) {
+  return LP == 64 ? fo_carry_bytes(l1, diff, M, nblk) : 0;
+}
 
 template <int DP, int W, int LP, int M, int SEED, bool MF = false>
 int launch_fo(const SigArgs &a, long long nblocks, hipStream_t s) {
   if (nblocks <= 0) return GPSIG_OK;
   constexpr bool DIFF = seed_is_diff(SEED);
-  const size_t lds = LP == 64 ? fo_carry_bytes(a.l1, DIFF, M, a.nblk) : 0;
+  const size_t lds = fo_launch_lds(LP, a.l1, DIFF, M, a.nblk);
   if (lds > FO_MAX_CARRY_BYTES) return GPSIG_EUNSUPPORTED;
   if (a.pair_mode == GPSIG_PAIRS_DIAG) {
     hipLaunchKernelGGL((sig_fo_kernel<DP, W, LP, M, SEED, true, false, MF>), dim3((unsigned)nblocks), dim3(256), lds, s, a);

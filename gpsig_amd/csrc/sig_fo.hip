@@ -56,16 +56,41 @@ int features(const float *X, int n, int l, int d, int DP, float *F, hipStream_t 
       DP, [&](auto dp) { return launch_features<decltype(dp)::value>(X, n, l, d, F, s); });
 }
 
+// the geometry of a launch and its column blocks (W = 0: none)
+static Geo fo_launch_geo(int l2, int DP, int M, bool mf, bool split, int seed, int *nblk) {
+  const Geo g = DP == 0 ? fo_geometry_wide(l2, seed) : fo_geometry(l2, DP, M, mf, split ? -1 : seed);
+  *nblk = g.W == 0 ? 0 : fo_blocks(l2, seed_is_diff(seed), g);
+  return g;
+}
+
 int sig_fo_launch(const SigArgs &a0, int DP, int seed, long long nblocks, hipStream_t s) {
-  const Geo g = DP == 0 ? fo_geometry_wide(a0.l2, seed) : fo_geometry(a0.l2, DP, a0.M, a0.mfma != 0, a0.dmbuf ? -1 : seed);
-  if (g.W == 0) return GPSIG_EUNSUPPORTED;
   SigArgs a = a0;
-  a.nblk = fo_blocks(a0.l2, seed_is_diff(seed), g);
+  const Geo g = fo_launch_geo(a0.l2, DP, a0.M, a0.mfma != 0, a0.dmbuf != nullptr, seed, &a.nblk);
+  if (g.W == 0) return GPSIG_EUNSUPPORTED;
   return dispatch<0, 1, 2, 3, 4, 5, 6, 8>(DP, [&](auto dp) {
     return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(a.M, [&](auto m) {
       return sig_fo_launch_dpm<decltype(dp)::value, decltype(m)::value>(a, seed, nblocks, s);
     });
   });
+}
+
+// gpsig_sig_fo_route, one launch of the plain kernels (no matrix-core seed, no split diagnostic): the geometry
+// and column blocks of sig_fo_launch, the carries of launch_fo and the codes the two return on the way
+int sig_fo_route(int l1, int l2, int DP, int M, int seed, bool diag, bool state, long long nblocks, FoRoute *r) {
+  int nblk;
+  const Geo g = fo_launch_geo(l2, DP, M, false, false, seed, &nblk);
+  if (g.W == 0) return GPSIG_EUNSUPPORTED;
+  r->W = g.W;
+  r->LP = g.LP;
+  r->nblk = nblk;
+  r->carry = fo_launch_lds(g.LP, l1, seed_is_diff(seed), M, nblk);
+  if (DP == 7 || DP < 0 || DP > 8 || M < 1 || M > FO_MAX_LEVELS) return GPSIG_EUNSUPPORTED;  // no instantiation
+  if (nblocks <= 0) return GPSIG_OK;
+  if (r->carry > FO_MAX_CARRY_BYTES) return GPSIG_EUNSUPPORTED;
+  if (!diag && state && (!seed_is_diff(seed) || seed_is_radial(seed))) return GPSIG_EUNSUPPORTED;
+  r->workgroups += nblocks;
+  r->launches += 1;
+  return GPSIG_OK;
 }
 
 int fo_lanes_per_pair(int l2, int DP, int M, bool mf, int seed, bool split) {

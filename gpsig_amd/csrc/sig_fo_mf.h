@@ -119,6 +119,23 @@ struct MfArgs {
 };
 // Column-blocked launches are chunked so that the carry scratch stays bounded
 constexpr int MF_BLK_CHUNK = 256;
+// launches of nblocks workgroups: the chunks of a column-blocked launch, else one
+inline long long mf_launches(int nblk, long long nblocks) {
+  return nblk > 1 ? (nblocks + MF_BLK_CHUNK - 1) / MF_BLK_CHUNK : 1;
+}
+// Workgroups over the rows [row_begin, row_end) in pair mode RECT / UPPER: xb x-sequences against single
+// y-sequences (not pair_tiles: xb, not 4, x-sequences per workgroup; tile_base also for RECT).  Tile row r of
+// UPPER holds the y-sequences b >= xb r, so P(r) = r n2 - xb r (r - 1) / 2 tiles lie before it.
+inline long long mf_tiles(int pair_mode, int row_begin, int row_end, int n2, int xb, long long *tile_base) {
+  const int t0 = row_begin / xb, t1 = (row_end + xb - 1) / xb;
+  if (pair_mode == GPSIG_PAIRS_UPPER) {
+    auto P = [&](long long r) { return r * n2 - (long long)xb * r * (r - 1) / 2; };
+    *tile_base = P(t0);
+    return P(t1) - P(t0);
+  }
+  *tile_base = (long long)t0 * n2;
+  return (long long)(t1 - t0) * n2;
+}
 inline int mf_cw(int M) { return M <= 5 ? 4 : 8; }
 inline size_t mf_carry_bytes(int l1, int nw) { return (size_t)MF_BLK_CHUNK * nw * MF_G * (size_t)(l1 > 1 ? l1 - 1 : 1) * 8 * sizeof(float); }
 

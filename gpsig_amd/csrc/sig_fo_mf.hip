@@ -167,21 +167,35 @@ int sig_fo_mf(const SigArgs &a0, int d, int seed, float *scratch, hipStream_t s)
   m.cw = mf_cw(a0.M);
   if (m.nblk > 1 && a0.M > 1 && !scratch) return GPSIG_EWORKSPACE;
   const int xb = mf_waves(d, a0.l2) * MF_G;  // x-sequences per workgroup
-  const int t0 = a0.row_begin / xb, t1 = (a0.row_end + xb - 1) / xb;
-  // not pair_tiles: xb (not 4) x-sequences per workgroup against single y-sequences, tile_base also for RECT
-  long long nblocks;
-  if (a0.pair_mode == GPSIG_PAIRS_UPPER) {
-    auto P = [&](long long r) { return r * a0.n2 - (long long)xb * r * (r - 1) / 2; };
-    m.p.tile_base = P(t0);
-    nblocks = P(t1) - P(t0);
-  } else {
-    m.p.tile_base = (long long)t0 * a0.n2;
-    nblocks = (long long)(t1 - t0) * a0.n2;
-  }
+  const long long nblocks = mf_tiles(a0.pair_mode, a0.row_begin, a0.row_end, a0.n2, xb, &m.p.tile_base);
   if (nblocks <= 0) return GPSIG_OK;
   if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;
   return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(
       a0.M, [&](auto lv) { return sig_fo_mf_launch_m<decltype(lv)::value>(m, seed, nblocks, s); });
+}
+
+// gpsig_sig_fo_route: the geometry, tiles and launches of sig_fo_mf (and of mf_launch_nw under it) for the rows
+// [row_begin, row_end), and its return; no launches for an empty row window (the entry returns before)
+int sig_fo_mf_route(int n2, int l1, int l2, int d, int M, int seed, int pair_mode, int row_begin, int row_end,
+                    FoRoute *r) {
+  if (!mf_applies(d, l2) || pair_mode == GPSIG_PAIRS_DIAG || l1 < 2) return GPSIG_EUNSUPPORTED;
+  const MfGeo g = mf_geo(d, l2);
+  r->W = mf_w(l2);
+  r->LP = MF_LP;
+  r->nblk = mf_nblk(l2);
+  r->nw = g.nw;
+  r->np = g.np;
+  r->cw = mf_cw(M);
+  r->xb = mf_waves(d, l2) * MF_G;
+  if (row_end == row_begin) return GPSIG_OK;
+  long long tile_base;
+  const long long nblocks = mf_tiles(pair_mode, row_begin, row_end, n2, r->xb, &tile_base);
+  if (nblocks <= 0) return GPSIG_OK;
+  if (nblocks > 0x7fffffffLL || M < 1 || M > 8) return GPSIG_EUNSUPPORTED;
+  if (seed != SEED_RBF_DIFF && seed != SEED_LIN_DIFF) return GPSIG_EUNSUPPORTED;
+  r->workgroups = nblocks;
+  r->launches = (int)mf_launches(r->nblk, nblocks);
+  return GPSIG_OK;
 }
 
 // The RBF difference-seed cells of the pairs of rows [row_begin, row_end) (pair_mode RECT / UPPER: against every
@@ -218,15 +232,7 @@ int sig_fo_mf_cells(const float *FX, int n1, int l1, const float *FY, int n2, in
     m.p.tile_base = 0;
     nblocks = row_end - row_begin;
   } else {
-    const int t0 = row_begin / xb, t1 = (row_end + xb - 1) / xb;
-    if (pair_mode == GPSIG_PAIRS_UPPER) {
-      auto P = [&](long long r) { return r * n2 - (long long)xb * r * (r - 1) / 2; };
-      m.p.tile_base = P(t0);
-      nblocks = P(t1) - P(t0);
-    } else {
-      m.p.tile_base = (long long)t0 * n2;
-      nblocks = (long long)(t1 - t0) * n2;
-    }
+    nblocks = mf_tiles(pair_mode, row_begin, row_end, n2, xb, &m.p.tile_base);
   }
   if (nblocks <= 0) return GPSIG_OK;
   if (nblocks > 0x7fffffffLL) return GPSIG_EUNSUPPORTED;

@@ -30,7 +30,9 @@ static int mf_launch_nw(const MfArgs &a, long long nblocks, hipStream_t s) {
   if constexpr (W == 8) {
     if (a.nblk > 1) {  // column blocks: chunks of MF_BLK_CHUNK workgroups share the carry scratch
       MfArgs c = a;
-      for (long long b0 = 0; b0 < nblocks; b0 += MF_BLK_CHUNK) {
+      const long long nl = mf_launches(a.nblk, nblocks);
+      for (long long k = 0; k < nl; ++k) {
+        const long long b0 = k * MF_BLK_CHUNK;
         c.blk0 = b0;
         const long long nb = nblocks - b0 < MF_BLK_CHUNK ? nblocks - b0 : MF_BLK_CHUNK;
         const int rc = mf_launch_blk<NW, W, M, SEED, true>(c, nb, s);

@@ -335,6 +335,30 @@ def ho_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_level
     return r
 
 
+FO_ROUTE_KEYS = ("path", "DP", "W", "LP", "nblk", "carry_bytes", "pairs_per_wave", "xb", "nw", "np", "cw", "dtiles",
+                 "pairs_per_chunk", "workgroups", "launches")
+
+
+def fo_route(n1: int, l1: int, n2: int | None, l2: int | None, d: int, num_levels: int, base="rbf",
+             difference: bool = True, diag: bool = False, rows: tuple | None = None, state: bool = False) -> dict:
+    """What sig_gram / sig_diag at order 1 would run for a shape (gpsig_sig_fo_route: host only, no launch, no
+    device).  n2 None: the symmetric K(X) (diag=True: sig_diag); state: the saved-state launch.  path (0 fixed-channel
+    records, 1 runtime channel loop, 2 matrix-core Gram) and the other FO_ROUTE_KEYS as include/gpsig_amd.h describes
+    them.  Raises GpsigError where the launch would (unknown base kernels, the carries past the LDS, more than 8
+    levels)."""
+    import ctypes
+    sym = n2 is None
+    pm = L.PAIRS_DIAG if diag else (L.PAIRS_UPPER if sym else L.PAIRS_RECT)
+    if sym:
+        n2, l2 = n1, l1
+    r0, r1 = (0, n1) if rows is None else rows
+    out = (ctypes.c_int * len(FO_ROUTE_KEYS))()
+    rc = L.load().gpsig_sig_fo_route(n1, l1, n2, l2, d, num_levels, base_kind(base), int(bool(difference)), pm, r0, r1,
+                                     int(bool(state)), out)
+    L.check(rc, "gpsig_sig_fo_route")
+    return dict(zip(FO_ROUTE_KEYS, out))
+
+
 HO_VJP_KERNELS = ("REG", "LDS", "SPLIT4", "SPLIT8")
 
 

@@ -399,6 +399,37 @@ int gpsig_sig_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, in
 int gpsig_sig_vjp_ho_route(int n1, int l1, int n2, int l2, int d, int num_levels, int order, int base_kind,
                            int pair_mode, int row_begin, int row_end, int *out);
 
+/* The same for the first-order fp32 Gram and diagonal (gpsig_sig_gram / gpsig_sig_diag at order 1; state != 0:
+ * gpsig_sig_gram_state), with the arguments that call decides by.  Three kernel paths: up to 8 channels the
+ * fixed-channel feature records; past 8 the runtime channel loop, except that the RBF and linear difference seeds in
+ * pair modes RECT and UPPER run the matrix-core Gram while its B image and tiles fit 160 KiB of LDS.
+ * out: GPSIG_SIG_FO_ROUTE_INTS ints:
+ *   out[0]  path: 0 fixed-channel records, 1 runtime channel loop, 2 matrix-core Gram
+ *   out[1]  DP (channel instantiation 1..6 or 8; 0 past 8 channels)
+ *   out[2]  W (columns per lane: 2, 4, 8, or 10)
+ *   out[3]  LP (lanes per pair: 16, 32, 64; 10: the 10-lane groups of 65..100 points; matrix cores: 16)
+ *   out[4]  column blocks (of LP W - 1 cells; 1: the sequence fits one lane group)
+ *   out[5]  carry bytes: paths 0 and 1 the dynamic LDS of a blocked launch (4 waves x rows x (num_levels - 1)
+ *           floats), path 2 the carry region of the workspace (column blocks only); clamped to INT_MAX
+ *   out[6]  pairs per wave on paths 0 and 1 (64 / LP; 6 for LP = 10; 1 in pair mode DIAG), 0 on path 2
+ *   out[7]  xb, the x-sequences of one workgroup on path 2 (4 nw, against one y-sequence), else 0
+ *   out[8]  nw, waves per workgroup on path 2 (8, or 4 where the LDS is short), else 0
+ *   out[9]  np, f16 parts per GEMM operand on path 2 (2; 3 with GPSIG_MF_PARTS=3 where they fit), else 0
+ *   out[10] cw, floats per carry row on path 2 (4 up to 5 levels, else 8), else 0
+ *   out[11] 1: the wide diagonal runs on seed tiles (path 1, DIAG, RBF difference seed, one column block), else 0
+ *   out[12] pairs per chunk of seed tiles (512 MiB of tiles, at most the n of the call), 0 without tiles
+ *   out[13] workgroups over all launches (clamped to INT_MAX)   out[14] kernel launches (chunks of 256 workgroups
+ *           for a column-blocked path 2, one per chunk of seed tiles); both 0 for an empty row window
+ * GPSIG_FO_FIXED_MAX, GPSIG_WIDE_MF, GPSIG_MF_PARTS and GPSIG_MF_NW are read once per process; the query tells
+ * what this process runs.  Returns GPSIG_OK; GPSIG_EINVAL for arguments the call rejects (state != 0 with
+ * difference = 0, pair mode DIAG, or UPPER on unequal shapes); GPSIG_EUNSUPPORTED where the call returns it:
+ * unknown base kinds, num_levels past 8, a saved state for the Matern kinds, carries past 160 KiB (out is filled
+ * then, so out[5] shows the size), and for the GPSIG_BASE_SEED_MFMA / GPSIG_GRAM_SPLIT variants, which the query
+ * does not describe. */
+#define GPSIG_SIG_FO_ROUTE_INTS 15
+int gpsig_sig_fo_route(int n1, int l1, int n2, int l2, int d, int num_levels, int base_kind, int difference,
+                       int pair_mode, int row_begin, int row_end, int state, int *out);
+
 /* ---------------------------------------------------------------------------------------------
  * Float64 evaluation of the first-order Gram and diagonal (order 1): double inputs, double arithmetic, double
  * outputs, for K that goes into a Cholesky factorisation, for unstandardised data (point offsets of many

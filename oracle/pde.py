@@ -21,8 +21,16 @@ _lib = None
 def build(force: bool = False) -> str:
     os.makedirs(os.path.dirname(_SO), exist_ok=True)
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(_SRC):
-        subprocess.check_call(["gcc", "-O2", "-fopenmp", "-fPIC", "-shared", "-ffp-contract=off",
-                               _SRC, "-o", _SO, "-lm"])
+        # Several processes can get here at once (the ranks of a multi-process test): each links into a file of
+        # its own and renames it into place, so a loader never opens a half-written library.
+        tmp = f"{_SO}.{os.getpid()}.tmp"
+        try:
+            subprocess.check_call(["gcc", "-O2", "-fopenmp", "-fPIC", "-shared", "-ffp-contract=off",
+                                   _SRC, "-o", tmp, "-lm"])
+            os.replace(tmp, _SO)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     return _SO
 
 

@@ -19,7 +19,7 @@ def header_symbols():
 def test_header_declares_expected_entry_points():
     syms = header_symbols()
     for s in ["gpsig_sig_gram", "gpsig_sig_diag", "gpsig_pde_gram", "gpsig_pde_diag", "gpsig_pde_route",
-              "gpsig_sig_ho_route", "gpsig_tens_vs_seq",
+              "gpsig_sig_ho_route", "gpsig_sig_fo_route", "gpsig_tens_vs_seq",
               "gpsig_tens_gram", "gpsig_rescaled", "gpsig_sym_assemble", "gpsig_version"]:
         assert s in syms, s
 
@@ -199,6 +199,36 @@ def test_sig_ho_route_query_without_gpu(monkeypatch):
     assert route(4, 45, 2, 40, 4, 8, 8, "linear")[-1] is False             # 87380 coordinates
     monkeypatch.setattr(ops, "SIG_FEATURE_MAX", 0)
     assert route(4, 74, 2, 70, 3, 8, 8, "linear")[-1] is False
+
+
+def test_sig_fo_route_argument_checks_without_gpu():
+    """gpsig_sig_fo_route is host only and returns what gpsig_sig_gram / gpsig_sig_diag / gpsig_sig_gram_state return
+    for the same arguments (the route table itself: tests/test_fo_routes.py)."""
+    import gpsig_amd._lib as L
+    lib = L.load()
+    out = (ctypes.c_int * 15)()
+
+    def rc(n1=4, l1=45, n2=2, l2=40, d=3, M=4, base=L.BASE_RBF, diff=1, pm=L.PAIRS_RECT, r0=0, r1=4, state=0, o=out):
+        return lib.gpsig_sig_fo_route(n1, l1, n2, l2, d, M, base, diff, pm, r0, r1, state, o)
+    assert rc() == L.GPSIG_OK and out[13] == 1 and out[14] == 1   # one workgroup: 4 x-sequences x 4 pairs per wave
+    assert rc(o=None) == L.GPSIG_EINVAL
+    assert rc(M=0) == L.GPSIG_EINVAL
+    assert rc(l2=1) == L.GPSIG_EINVAL                       # difference needs two points
+    assert rc(l2=1, diff=0) == L.GPSIG_OK                   # the point seeds take one
+    assert rc(d=0) == L.GPSIG_EINVAL
+    assert rc(r1=5) == L.GPSIG_EINVAL                       # row window past n1
+    assert rc(r0=3, r1=2) == L.GPSIG_EINVAL
+    assert rc(pm=L.PAIRS_UPPER) == L.GPSIG_EINVAL           # UPPER pairs X with itself: equal shapes
+    assert rc(pm=3) == L.GPSIG_EINVAL
+    assert rc(state=1, diff=0) == L.GPSIG_EINVAL            # gpsig_sig_gram_state: difference seeds, RECT / UPPER
+    assert rc(n2=4, l2=45, pm=L.PAIRS_DIAG, state=1) == L.GPSIG_EINVAL
+    assert rc(state=1) == L.GPSIG_OK
+    assert rc(base=7) == L.GPSIG_EUNSUPPORTED
+    assert rc(M=9) == L.GPSIG_EUNSUPPORTED
+    assert rc(M=9, r1=0) == L.GPSIG_OK                      # no rows: the call returns before it meets the level count
+    assert rc(base=L.BASE_MATERN32, state=1) == L.GPSIG_EUNSUPPORTED
+    assert rc(base=L.BASE_RBF | L.BASE_SEED_MFMA) == L.GPSIG_EUNSUPPORTED
+    assert rc(base=L.BASE_RBF | L.GRAM_SPLIT) == L.GPSIG_EUNSUPPORTED
 
 
 def _ho_vjp_slots(o, M):

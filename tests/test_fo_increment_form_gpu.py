@@ -57,27 +57,38 @@ def check_all(X, M, X2=None, diag=True):
         assert_levels(k.Kdiag(t(Xf), return_levels=True).cpu().numpy(), ref.Kdiag(Xf, return_levels=True), "Kdiag")
 
 
-# (L, D, M, N): columns per lane x lanes per pair of the launch that L points take
+# (L, D, M, N, (W, LP, column blocks)): columns per lane x lanes per pair of the launch that L points take
 ROUTES = [
-    (9, 5, 5, 9),      # 2 x 16
-    (33, 5, 5, 13),    # 4 x 16 (L2 = 30: 2 x 16)
-    (64, 5, 5, 9),     # 4 x 16, every column a point
-    (100, 5, 5, 13),   # 10 x 10: groups off the DPP rows, u_i0 through the LDS crossbar
-    (128, 5, 5, 9),    # 8 x 16: the headline geometry, u_i0 by the DPP row broadcast
-    (200, 5, 5, 13),   # 8 x 32: two DPP rows per group
-    (300, 5, 5, 9),    # 8 x 64, one column block: level 1 scanned
-    (600, 5, 5, 9),    # 8 x 64, two column blocks: level 1 scanned, carries through LDS
-    (128, 8, 5, 13),   # D = 8: the points of column pairs >= 1 re-read on exact rows
-    (128, 5, 1, 9),    # level 1 only (closed form, no recursion)
-    (128, 5, 2, 13),   # level 2 reads the closed-form prefix and nothing is scanned
-    (128, 5, 3, 9),    # one scanned level beside the closed-form one
+    (9, 5, 5, 9, (2, 16, 1)),      # 2 x 16
+    (33, 5, 5, 13, (4, 16, 1)),    # 4 x 16 (L2 = 30: 2 x 16)
+    (64, 5, 5, 9, (4, 16, 1)),     # 4 x 16, every column a point
+    (100, 5, 5, 13, (10, 10, 1)),  # 10 x 10: groups off the DPP rows, u_i0 through the LDS crossbar
+    (128, 5, 5, 9, (8, 16, 1)),    # 8 x 16: the headline geometry, u_i0 by the DPP row broadcast
+    (200, 5, 5, 13, (8, 32, 1)),   # 8 x 32: two DPP rows per group
+    (300, 5, 5, 9, (8, 64, 1)),    # 8 x 64, one column block: level 1 scanned
+    (600, 5, 5, 9, (8, 64, 2)),    # 8 x 64, two column blocks: level 1 scanned, carries through LDS
+    (128, 8, 5, 13, (8, 16, 1)),   # D = 8: the points of column pairs >= 1 re-read on exact rows
+    (128, 5, 1, 9, (8, 16, 1)),    # level 1 only (closed form, no recursion)
+    (128, 5, 2, 13, (8, 16, 1)),   # level 2 reads the closed-form prefix and nothing is scanned
+    (128, 5, 3, 9, (8, 16, 1)),    # one scanned level beside the closed-form one
 ]
 
 
-@pytest.mark.parametrize("L,D,M,N", ROUTES)
+def geometry(L, D, M, **kw):
+    """(W, LP, column blocks) of the fixed-channel launch that K(X) of L points takes (ops.fo_route: host only)."""
+    from gpsig_amd import ops
+    r = ops.fo_route(6, L, None, None, D, M, **kw)
+    assert r["path"] == 0, r
+    return r["W"], r["LP"], r["nblk"]
+
+
+@pytest.mark.parametrize("L,D,M,N", [r[:4] for r in ROUTES])
 def test_routes(L, D, M, N):
     """N = 9 and 13 leave the tiles of 4 sequences by 4 pairs (16-lane groups) or 6 pairs (10-lane groups)
     partly filled; X2 has L - 3 points, so the columns past the sequence sit inside a lane's chain."""
+    geo = {r[:4]: r[4] for r in ROUTES}[L, D, M, N]
+    assert geometry(L, D, M) == geo and geometry(L, D, M, diag=True) == geo
+    assert geometry(L - 3, D, M) == ((2, 16, 1) if L == 33 else geo)
     X = walks(N, L, D, 1000 + L + D + M)
     X2 = walks(N - 2, L - 3, D, 2000 + L + D + M)
     check_all(X, M, X2)
@@ -85,6 +96,7 @@ def test_routes(L, D, M, N):
 
 def test_route_d8_m6():
     """D = 8, M = 6 (8 x 16 at two waves per SIMD, four scanned levels beside the closed-form one), K(X) only."""
+    assert geometry(128, 8, 6) == (8, 16, 1)
     check_all(walks(9, 128, 8, 77), 6, diag=False)
 
 
@@ -121,6 +133,7 @@ def test_regimes(name, L):
 
 def test_anchor_rows_inside_a_pair():
     """L = 300: the anchor rows 127 and 255 reset k and expm1(q) inside a pair, on jumpy data too."""
+    assert geometry(300, 5, 5) == geometry(300, 5, 4) == (8, 64, 1)
     check_all(regime("walks", 9, 300), 5, diag=False)
     check_all(regime("jumps", 9, 300), 4, diag=False)
 
@@ -128,6 +141,7 @@ def test_anchor_rows_inside_a_pair():
 def test_anchor_rows_with_the_closed_form_prefix():
     """L = 200 (two DPP rows per group): the anchor row 127 falls inside a pair that takes level 1 from u, and u
     goes on from the exact rows' difference."""
+    assert geometry(200, 5, 5) == geometry(200, 5, 4) == (8, 32, 1)
     check_all(regime("walks", 9, 200), 5, diag=False)
     check_all(regime("jumps", 9, 200), 4, diag=False)
 
@@ -151,6 +165,7 @@ def test_saved_state_launch_writes_the_same_gram(L):
     the column sums of level 1 only for the state it stores: the same Gram, bit for bit."""
     from gpsig_amd import ops
     N, D, M = 6, 5, 5
+    assert geometry(L, D, M, state=True) == {40: (4, 16, 1), 100: (10, 10, 1), 128: (8, 16, 1), 200: (8, 32, 1)}[L]
     X3 = t(walks(N, L, D, 56)).float()
     state = torch.empty(ops.sig_state_numel(N, None, L, M), dtype=torch.float32, device=DEV)
     assert torch.equal(ops.sig_gram(X3, None, M, state=state), ops.sig_gram(X3, None, M))

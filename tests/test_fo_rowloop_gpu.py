@@ -57,7 +57,12 @@ def test_prefetch_ends_and_anchor_positions(L, D, M):
     """Rows = L - 1: one row; two; 127 (no anchor row); 128 (the anchor row is the last row, the prefetch index
     clamps on it); 129 (one row after an anchor row); 256 (two anchor rows).  D = 8 re-reads the points of
     column pairs >= 1 on exact rows; L = 100 takes the 10-lane groups.  D = 8, M = 7 takes 4 columns per lane
-    on 64 lanes at L = 130 (across an anchor row) and 2 columns per lane at L = 128."""
+    on 64 lanes at L = 130 (across an anchor row) and 4 columns per lane on 32 lanes at L = 128."""
+    from gpsig_amd import ops
+    r = ops.fo_route(6, L, None, None, D, M)
+    want = (10, 10) if L == 100 else ((4, 64) if L == 130 else (4, 32)) if (D, M) == (8, 7) else \
+        (2, 16) if L <= 3 else (8, 16) if L == 128 else (8, 32) if L <= 130 else (8, 64)
+    assert (r["path"], r["W"], r["LP"], r["nblk"]) == (0,) + want + (1,), r
     check_K(smooth(6, L, D, 100 + L + D), M)
 
 
@@ -83,6 +88,9 @@ def test_consecutive_slow_rows(D, every_seq):
 def test_slow_rows_four_columns_per_lane(L):
     """The slow-row data at D = 8, M = 7: 4 columns per lane, in one column block at L = 130 and in two (the
     row carries between them through LDS) at L = 260."""
+    from gpsig_amd import ops
+    r = ops.fo_route(5, L, None, None, 8, 7)
+    assert (r["path"], r["W"], r["LP"], r["nblk"]) == (0, 4, 64, 1 if L == 130 else 2), r
     check_K(jumpy(5, L, 8, SLOW_ROWS, [0], 13), 7)
 
 

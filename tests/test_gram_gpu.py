@@ -114,6 +114,13 @@ def test_lengths_and_geometries(L):
     from gpsig_amd import ops
     rng = np.random.default_rng(L)
     N1, N2, D, M = 5, 3, 4, 4
+    # (W, LP) of K(X) at L points and of K(X, Y) at Y's L - 1: the list sits on both sides of every seam
+    geo = {2: (2, 16), 3: (2, 16), 17: (2, 16), 33: (4, 16), 64: (4, 16), 65: (10, 10), 81: (10, 10), 100: (10, 10),
+           101: (8, 16), 128: (8, 16), 129: (8, 32), 200: (8, 32), 257: (8, 64), 300: (8, 64)}
+    geo_y = {**geo, 33: (2, 16), 65: (4, 16), 101: (10, 10), 129: (8, 16), 257: (8, 32)}
+    r, ry = ops.fo_route(N1, L, None, None, D, M), ops.fo_route(N1, L, N2, max(L - 1, 2), D, M)
+    assert (r["path"], r["W"], r["LP"], r["nblk"]) == (0,) + geo[L] + (1,), r
+    assert (ry["path"], ry["W"], ry["LP"], ry["nblk"]) == (0,) + geo_y[L] + (1,), ry
     X = np.cumsum(rng.standard_normal((N1, L, D)), 1) / np.sqrt(L * D)
     Y = np.cumsum(rng.standard_normal((N2, max(L - 1, 2), D)), 1) / np.sqrt(L * D)
     ref = kr.SignatureKernelRef(L * D, D, M, normalization=False)
@@ -144,6 +151,10 @@ def test_ten_lane_groups_tiles(N):
     from gpsig_amd import ops
     rng = np.random.default_rng(7 * N)
     L, D, M = 100, 5, 5
+    r = ops.fo_route(N, L, None, None, D, M)
+    assert (r["path"], r["W"], r["LP"], r["pairs_per_wave"]) == (0, 10, 10, 6), r
+    # tile row r of 4 x-sequences starts at the tile of 6 y-sequences that holds b = 4 r
+    assert r["workgroups"] == sum((N + 5) // 6 - 4 * k // 6 for k in range((N + 3) // 4)), r
     X = np.cumsum(rng.standard_normal((N, L, D)), 1) / np.sqrt(L * D)
     ref = kr.SignatureKernelRef(L * D, D, M, normalization=False)
     got = ops.sig_gram(t(X), None, M).cpu().numpy()

@@ -33,6 +33,12 @@ def test_wide_rbf_gram_and_diag(D, L):
     from gpsig_amd import ops
     rng = np.random.default_rng(D * 1000 + L)
     M = 4
+    # K(X) on the matrix cores: columns per lane, column blocks of 127 cells, waves per workgroup by the LDS
+    W, nblk, nw = {(33, 20): (4, 1, 8), (46, 136): (10, 1, 8), (126, 136): (10, 1, 4), (46, 500): (8, 4, 8),
+                   (126, 64): (4, 1, 8), (200, 30): (4, 1, 8)}[D, L]
+    r, rd = ops.fo_route(5, L, None, None, D, M), ops.fo_route(5, L, None, None, D, M, diag=True)
+    assert (r["path"], r["W"], r["nblk"], r["nw"]) == (2, W, nblk, nw), r
+    assert (rd["path"], rd["dtiles"], rd["nblk"]) == (1, 1, 1), rd   # the diagonal: channel loop on seed tiles
     X = walks(rng, 5, L, D)
     Y = walks(rng, 3, max(L - 7, 2), D)
     ref = kr.SignatureKernelRef(L * D, D, M, normalization=False)
@@ -462,6 +468,12 @@ def test_wide_mf_column_blocks(D, L, M, base):
     block through the workspace; K(X, X2) at ragged lengths and K(X), raw levels against the oracle."""
     from gpsig_amd import ops
     rng = np.random.default_rng(D + L + M)
+    r, ry = ops.fo_route(5, L, None, None, D, M, base), ops.fo_route(5, L, 3, L - 11, D, M, base)
+    assert (r["path"], r["W"], r["nblk"], r["nw"], r["cw"]) == \
+        (2, 8, 2 if L < 256 else 3, 4 if D == 200 else 8, 4 if M <= 5 else 8), r
+    # Y's L - 11 points: 150 take one block of 10 columns per lane, 289 three blocks, and 159 at 200 channels the
+    # channel loop (the B image of 160 columns is past the LDS there)
+    assert (ry["path"], ry["W"], ry["nblk"]) == {161: (2, 10, 1), 300: (2, 8, 3), 170: (1, 8, 1)}[L], ry
     X = walks(rng, 5, L, D)
     Y = walks(rng, 3, L - 11, D)
     ref = kr.SignatureKernelRef(L * D, D, M, normalization=False, base=base)
@@ -505,6 +517,8 @@ def test_wide_split_operand_scales(case):
     from gpsig_amd import ops
     rng = np.random.default_rng(["offset", "tiny", "huge_lin", "zero_seq"].index(case) + 900)
     D, L, M = 46, 40, 4
+    for r in (ops.fo_route(5, L, None, None, D, M), ops.fo_route(5, L, 3, L - 5, D, M, "linear")):
+        assert (r["path"], r["W"], r["nw"], r["np"]) == (2, 4, 8, 2), r
     X = walks(rng, 5, L, D)
     Y = walks(rng, 3, L - 5, D)
     base = "rbf"
@@ -539,6 +553,8 @@ def test_wide_matrix_core_level_counts(M, L):
     from gpsig_amd import ops
     rng = np.random.default_rng(M * 100 + L)
     D = 40
+    for r in (ops.fo_route(4, L, None, None, D, M), ops.fo_route(4, L, 3, L - 3, D, M)):
+        assert (r["path"], r["W"], r["nblk"], r["cw"]) == (2, 4 if L == 60 else 10, 1, 4 if M <= 5 else 8), r
     X = walks(rng, 4, L, D)
     Y = walks(rng, 3, L - 3, D)
     ref = kr.SignatureKernelRef(L * D, D, M, normalization=False)
